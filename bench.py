@@ -11,7 +11,20 @@ HBM.  One step = FwdNTTTo then InvNTTTo over the whole batch (2048 transforms). 
 (one forward or one inverse transform of one polynomial), whole job.  Scaling: weak (each rank
 owns its own 1024 polys; no data-path collective).
 
-Secondary lines in the same JSON object (also measured, not the headline value):
+A plain run does only what the headline needs: set up, prewarm + warm up, time `--steps` steps,
+write `--dump-outputs DIR` if given, print the line.  Everything below (secondary lines, compute
+floors, CPU baselines) runs only with `--full`.
+
+--dump-outputs DIR: after the timed steps, what the headline's timed path computed in its last
+step, as DIR/<name>.npy (float64, exact): a fixed seeded sample of 2^20 of the batch's coefficients
+(all of them if the batch is smaller).  `sample_index` holds their flat indices
+(poly * N + coefficient); `ntt_step_out` the buffer after the last timed step (FwdNTTTo then
+InvNTTTo in place) at those indices; `ntt_fwd_out` one more forward transform of that buffer,
+out of place and untimed, at the same indices (the step's own forward result is overwritten by its
+inverse).  A 64-bit residue r is stored as the pair (r mod 2^32, r div 2^32).  The inputs are the
+same SplitMix64 stream in every run with the same arguments.
+
+Secondary lines in the same JSON object with --full (also measured, not the headline value):
   * l4_ntt: the same fwd+inv step at the Jindo default 255-bit prime (configs[3]), batch 64
   * jindo_commit: device-resident Jindo commits/s at targetN 2^14 (configs[2])
   * jindo_commit_2e16 (+ jindo_evaluate_2e16): the configs[4] shape, 512 commits per GPU
@@ -24,7 +37,7 @@ traffic / valu: per-line HBM bytes (rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE) an
 instruction counts (SQ_INSTS_VALU) from profiles/kernel_counters.json, which
 tools/profile_bench.sh writes for the libringo.so it profiled; reported only when that file's
 library hash equals the library this run loaded (else null, "stale").
-cpu_baseline: the C restatement (oracle/liboracle.so, threads) timed on this host on bounded
+cpu_baseline (--full): the C restatement (oracle/liboracle.so, threads) timed on this host on bounded
 samples of the NTT headline and of the configs[2] Jindo commit.
 """
 import argparse
@@ -85,11 +98,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--logn", type=int, default=16)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the L=4 / Jindo lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary lines (--extra), the compute-floor probes and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the headline's last timed step's output to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the L=4 / Jindo lines")
     ap.add_argument("--extra", default="l4,wide,j14,j16",
-                    help="secondary lines to run: l4, wide, j14, j16 (comma list)")
-    ap.add_argument("--no-ntt", action="store_true", help="skip the headline NTT line (profiling one line)")
+                    help="with --full: secondary lines to run: l4, wide, j14, j16 (comma list)")
+    ap.add_argument("--no-ntt", action="store_true",
+                    help="with --full: skip the headline NTT line (profiling one line)")
     ap.add_argument("--no-prewarm", action="store_true", help="no time-based prewarm (deterministic step count)")
     ap.add_argument("--plumbing", action="store_true",
                     help="CPU-only launcher/timing check: gloo ranks, a trivial host step, no GPU, no libringo")
@@ -97,7 +115,10 @@ def parse():
     ap.add_argument("--j16-batch", type=int, default=512,
                     help="commits per GPU per step, configs[4] shape (4096 commits / 8 GPUs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.no_ntt and not args.full and not args.plumbing:
+        ap.error("--no-ntt leaves nothing to run without --full (the secondary lines need it)")
+    return args
 
 
 class Events:
@@ -138,7 +159,35 @@ def prewarm(torch, fn, seconds=0.3):
     return n
 
 
-def ntt_step_bench(torch, ringo, dist, q, L, batch, logn, steps, warmup, seed):
+DUMP_SAMPLE, DUMP_SEED = 1 << 20, 0x44554D50  # 2^20 elements: 3 arrays, 40 MiB in all at L = 1
+
+
+def dump_outputs(torch, T, x, batch, N, L, stream, path, suffix):
+    """--dump-outputs: the step's output buffer x and one untimed out-of-place forward transform of
+    it, at a fixed seeded sample of element indices, as exact float64 (lo32, hi32) pairs per limb."""
+    total = batch * N
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+    didx = torch.from_numpy(idx).to(x.device)
+
+    def sample(t):  # [total * L] int64 words -> [n, L, 2] float64
+        w = t.view(total, L)[didx].cpu().numpy().view(np.uint64)
+        return np.stack([(w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)],
+                        axis=-1)
+
+    step_out = sample(x)
+    y = torch.empty_like(x)
+    T.fwd_dev(y, x, batch, stream)
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("sample_index", idx.astype(np.float64)), ("ntt_step_out", step_out),
+                      ("ntt_fwd_out", sample(y))):
+        np.save(os.path.join(path, name + suffix + ".npy"), arr)
+
+
+def ntt_step_bench(torch, ringo, dist, q, L, batch, logn, steps, warmup, seed, floor=False, dump=None):
     N = 1 << logn
     dev = torch.device("cuda", torch.cuda.current_device())
     F = ringo.Field(q)
@@ -173,8 +222,10 @@ def ntt_step_bench(torch, ringo, dist, q, L, batch, logn, steps, warmup, seed):
     wall = time.perf_counter() - t0
     ok = bool(torch.equal(x, ref))  # fwd then inv is the identity: full-size self-check
     kern_ms = ev.total_ms()
+    if dump is not None:
+        dump_outputs(torch, T, x, batch, N, L, stream, *dump)
     floor_ms = None
-    if logn == 16 and L in (1, 4):
+    if floor and logn == 16 and L in (1, 4):
         floor_ms = compute_floor(torch, ringo, q, L, N, batch, x, stream, steps, warmup)
         ok = ok and bool(torch.equal(x, ref))
     return dict(wall_s=wall, kernel_ms=kern_ms, ok=ok, ntts=2 * batch * steps, N=N, L=L, compute_floor_ms=floor_ms)
@@ -713,10 +764,14 @@ def main():
     C, csrc = counters()
     N = 1 << args.logn
     out = {}
-    extra = set() if args.no_extra else set(x for x in args.extra.split(",") if x)
+    full = args.full  # a plain run: the headline line only, no probes, no CPU legs
+    extra = set(x for x in args.extra.split(",") if x) if full and not args.no_extra else set()
     if not args.no_ntt:
+        dump = None
+        if args.dump_outputs:
+            dump = (args.dump_outputs, "" if world == 1 else "_rank%d" % rank)
         r = ntt_step_bench(torch, ringo, dist, P63, 1, args.batch, args.logn, args.steps, args.warmup,
-                           0x52494E47 + rank)
+                           0x52494E47 + rank, floor=full, dump=dump)
         ms_step, kern_ms = reduce_max(torch, dist, r["wall_s"] * 1000.0 / args.steps, r["kernel_ms"])
         ok = r["ok"]
         if dist is not None:
@@ -765,7 +820,7 @@ def main():
         })
     if "l4" in extra:
         st4 = max(2, args.steps // 2)
-        r4 = ntt_step_bench(torch, ringo, dist, Q255, 4, 64, args.logn, st4, 1, 7 + rank)
+        r4 = ntt_step_bench(torch, ringo, dist, Q255, 4, 64, args.logn, st4, 1, 7 + rank, floor=True)
         ms4, k4 = reduce_max(torch, dist, r4["wall_s"] * 1000.0 / st4, r4["kernel_ms"])
         vm = vec_mul_bench(torch, ringo, Q255, 4, 64 * N, 10, 11 + rank)
         tr4, vb4 = line_counters(C, "l4", 128, k4 / st4)
@@ -835,7 +890,7 @@ def main():
                           "batch combination + RCCL all-reduce of partial openBatches + partial evaluations + "
                           "responses; challenges injected" % jb,
                 "ms_per_evaluate": ems, "achieved_GBs": jr["eval"]["bytes_read"] / (ems / 1000.0) / 1e9}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         if not args.no_ntt:
             out["cpu_baseline"] = cpu_baseline(P63, 1, args.logn, args.cpu_seconds)
         if "j14" in extra:

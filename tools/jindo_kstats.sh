@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $2; do
   OUT=$R/gpurun_out/ks_$v
   export $1=$v
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python3 $R/bench.py --no-ntt --extra $LINE --no-cpu --steps 4 --warmup 1 > $OUT.json 2> $OUT.err || { echo "trace $v failed"; tail -5 $OUT.err; exit 1; }
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python3 $R/bench.py --full --no-ntt --extra $LINE --no-cpu --steps 4 --warmup 1 > $OUT.json 2> $OUT.err || { echo "trace $v failed"; tail -5 $OUT.err; exit 1; }
   f=$(find $OUT -name "*kernel_stats.csv" | head -1)
   echo "== $1=$v"
   python3 - "$f" <<'EOF'

@@ -9,7 +9,7 @@ ARGS=${@:---no-cpu --steps 4 --warmup 1}
 OUT=gpurun_out/$NAME
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/err.txt || { tail $OUT/err.txt; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --full $ARGS > $OUT/bench.json 2> $OUT/err.txt || { tail $OUT/err.txt; exit 1; }
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1); cp $f $OUT/kernel_stats.csv
 python3 - $OUT <<'PY'
 import csv, sys

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "${groups[@]}"; do
   i=$((i+1))
-  timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -o run -- python3 $R/bench.py --no-cpu --no-prewarm "$@" > $OUT/bench$i.json 2>$OUT/p$i.err || { echo "pmc pass $i failed"; tail -5 $OUT/p$i.err; exit 1; }
+  timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -o run -- python3 $R/bench.py --full --no-cpu --no-prewarm "$@" > $OUT/bench$i.json 2>$OUT/p$i.err || { echo "pmc pass $i failed"; tail -5 $OUT/p$i.err; exit 1; }
   echo "pass $i ok"
 done
 python3 $R/tools/pmc_summary.py $OUT
