@@ -1,5 +1,9 @@
-// ntt64.hpp -- single-word (q < 2^64/3, L = 1) NTT arithmetic for gfx950: lazy butterflies.
+// ntt64.hpp -- single-word (q < 2^63, L = 1) NTT arithmetic for gfx950: lazy butterflies.
 //
+// The bound is q < 2^63 (2q fits a word), not 2^64/3: the sum of two lazy values, < 4q < 2^65, is
+// compared against 2q through its carry bit (lazy_add's c, fwd_bfly_x / inv_bfly_x's c2), so 3q
+// may pass 2^64.  ntt_l1_lazy.hip gates on exactly this; tests/test_gpu_ntt_synthetic.py runs
+// q = 0x7ffffff900000001 (3q > 2^64) through every pass.
 // Values between butterfly stages live in [0, 2q) ("Harvey" lazy form); only the last stage of
 // a transform maps them to the canonical residues the reference produces (gnark fully reduces,
 // jindo/internal/zp/element.go:397-466), so every output limb is bit-identical to ntt.go.
@@ -20,7 +24,7 @@
 namespace rg {
 
 struct Q64 {
-  uint64_t q, q2;  // q, 2q (2q < 2^64 needs q < 2^63; the lazy add below needs q < 2^64/3)
+  uint64_t q, q2;  // q, 2q (2q < 2^64 needs q < 2^63; the lazy add below keeps the sum's 65th bit)
   uint32_t qhi;    // q >> 32
   uint32_t qlo1;   // q mod 2^32 == 1
 };
