@@ -184,6 +184,106 @@ rg_status rg_buckler_eval_circuit_dev(const rg_circuit* c, size_t rank, const ui
 rg_status rg_buckler_eval_circuit(const rg_circuit* c, size_t rank, const uint64_t* batch_const, const uint64_t* w,
                                   size_t n_w, const uint64_t* pw, size_t n_pw, uint64_t* out);
 
+/* ---- Buckler linear check and sum check (buckler/linear.go, buckler/prover.go:381-485) ---- */
+/* All results are canonical Montgomery elements, bit-identical to the reference.  Challenges and
+ * MustSetRandom draws are injected.  Every `_dev` entry validates its arguments before touching
+ * the device (RG_ERR_INVALID) and is asynchronous on `stream`; the forms without `_dev` take host
+ * pointers and are synchronous.
+ *
+ * LinearChecker (linear.go:12-17): a matrix M applied as TransformTo (M v) and TransposeTo (M^T v)
+ * on vectors [rank][L].  A checker is immutable after creation, except a projection checker's
+ * matrix (rg_buckler_checker_set_xof*; not concurrent with calls that use the checker).
+ *  - NewNTTChecker (linear.go:26-43): the negacyclic FwdNTT at rank; the transpose is
+ *    vOut[i] = v[rank-1-i] * SetUint64(rank), then InvNTT.  rank not a power of two is
+ *    RG_ERR_INVALID.
+ *  - NewAutChecker (linear.go:54-73): AutTo with idx (transform) or idx^-1 mod 2 rank (transpose,
+ *    modInverse linear.go:75-91), coefficient (ntt_domain = 0) or NTT domain.  An even idx or a
+ *    rank that is not a power of two is RG_ERR_INVALID.
+ *  - newProjChecker (linear.go:98-137): the 128 x rank boolean matrix, kept bit-packed on the
+ *    device (16 bytes per column).  rank < 128 is RG_ERR_INVALID.  The matrix is set from the raw
+ *    XOF bytes [rank][32] as the prover reads them (prover.go:168-176): entry (i, j) is true iff
+ *    bit i % 8 of byte i / 8 of column j's 32 bytes is 0.  A checker may be re-set; it is
+ *    RG_ERR_INVALID to apply one that was never set.
+ *  - newProjRecomposeChecker (linear.go:144-180): base [nb][L] = decomposeBase(bound)
+ *    (utils.go:7-32) as Montgomery elements < q, computed by the caller.  With g = rank / nb:
+ *    transform out[i] = sum_j base[j] v[i nb + j] (i < g), zero above; transpose
+ *    out[i nb + j] = base[j] v[i] (i < g), zero from g nb.  nb = 0 is RG_ERR_INVALID. */
+typedef struct rg_linchecker rg_linchecker;
+rg_status rg_buckler_checker_create_ntt(const rg_field* f, size_t rank, rg_linchecker** out);
+rg_status rg_buckler_checker_create_aut(const rg_field* f, size_t rank, long long idx, int ntt_domain,
+                                        rg_linchecker** out);
+rg_status rg_buckler_checker_create_proj(const rg_field* f, size_t rank, rg_linchecker** out);
+rg_status rg_buckler_checker_create_recompose(const rg_field* f, size_t rank, const uint64_t* base, size_t nb,
+                                              rg_linchecker** out);
+void rg_buckler_checker_destroy(rg_linchecker* c);
+rg_status rg_buckler_checker_set_xof_dev(rg_linchecker* c, const uint8_t* d_xof, void* stream);
+rg_status rg_buckler_checker_set_xof(rg_linchecker* c, const uint8_t* xof);
+/* TransformTo / TransposeTo on `batch` vectors, d_v [batch][rank][L] -> d_out [batch][rank][L];
+ * d_out == d_v is RG_ERR_INVALID.  The projection transform sums per-chunk partial rows in a fixed
+ * order (no atomics) and needs d_scratch of rg_buckler_checker_scratch_bytes(c, batch) bytes; the
+ * other kinds ignore d_scratch (0 bytes). */
+size_t rg_buckler_checker_scratch_bytes(const rg_linchecker* c, size_t batch);
+rg_status rg_buckler_checker_transform_dev(const rg_linchecker* c, uint64_t* d_out, const uint64_t* d_v, size_t batch,
+                                           uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_checker_transpose_dev(const rg_linchecker* c, uint64_t* d_out, const uint64_t* d_v, size_t batch,
+                                           void* stream);
+rg_status rg_buckler_checker_transform(const rg_linchecker* c, uint64_t* out, const uint64_t* v);
+rg_status rg_buckler_checker_transpose(const rg_linchecker* c, uint64_t* out, const uint64_t* v);
+/* linCheckVec (prover.go:409-413): out[0] = SetUint64(1), out[i] = out[i-1] * c, n elements. */
+rg_status rg_buckler_powers_dev(const rg_field* f, const uint64_t* d_c, size_t n, uint64_t* d_out, void* stream);
+rg_status rg_buckler_powers(const rg_field* f, const uint64_t* c, size_t n, uint64_t* out);
+/* Prover.sumCheckMask(maskRank) (prover.go:381-397) from the mask_rank injected draws d_rand, in
+ * the order the reference draws them: mask[k] = r[k] - r[k+rank] while k + rank < mask_rank, r[k]
+ * up to mask_rank, zero up to emb_rank; maskSum = r[0].  rank <= mask_rank <= emb_rank, and d_rand
+ * and d_mask may not alias (RG_ERR_INVALID). */
+rg_status rg_buckler_sumcheck_mask_dev(const rg_field* f, size_t rank, size_t mask_rank, size_t emb_rank,
+                                       const uint64_t* d_rand, uint64_t* d_mask, uint64_t* d_mask_sum, void* stream);
+rg_status rg_buckler_sumcheck_mask(const rg_field* f, size_t rank, size_t mask_rank, size_t emb_rank,
+                                   const uint64_t* rand, uint64_t* mask, uint64_t* mask_sum);
+/* The tail of linCheck / sumCheck / arithCheck (prover.go:439-458, 465-484, 401-403) on the NTT-domain
+ * d_eval [emb][L] (emb = the rank of the cyclic emb_plan; clobbered): eval *= scale (NULL: skipped,
+ * arithCheck), InvNTT, eval += mask [emb][L] (NULL: skipped), QuoRemByVanishing(eval, rank), then
+ * d_quo [n_quo][L] = quoPoly[:n_quo], d_rem_lo [rank-1][L] = rem[1..rank-1], d_rem_hi
+ * [jindo_rank][L] = jindo_rank - (rank-1) zeros, then remLo.  n_quo = rank (lin), sumCheckMaxRank -
+ * rank (sum), arithCheckMaxRank - rank (arith).  d_rem_lo and d_rem_hi may be NULL together
+ * (arithCheck discards the remainder); jindo_rank < rank - 1 is RG_ERR_INVALID.  d_scratch holds
+ * rg_buckler_check_finish_scratch_bytes(emb_plan) bytes; no two buffers may alias. */
+size_t rg_buckler_check_finish_scratch_bytes(const rg_ntt* emb_plan);
+rg_status rg_buckler_check_finish_dev(const rg_ntt* emb_plan, size_t rank, uint64_t* d_eval, const uint64_t* d_scale,
+                                      const uint64_t* d_mask, size_t n_quo, size_t jindo_rank, uint64_t* d_quo,
+                                      uint64_t* d_rem_lo, uint64_t* d_rem_hi, uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_check_finish(const rg_ntt* emb_plan, size_t rank, const uint64_t* eval, const uint64_t* scale,
+                                  const uint64_t* mask, size_t n_quo, size_t jindo_rank, uint64_t* quo,
+                                  uint64_t* rem_lo, uint64_t* rem_hi);
+/* Prover.linCheck (prover.go:406-459).  The handle holds what Compile fixes: the encoder's cyclic
+ * plan at the witness rank, the cyclic plan at the embedding rank, the ordered checkers
+ * (ctx.linCheckers) and, for checker c, its ordered witness-ID pairs pairs[pair_off[c] ..
+ * pair_off[c+1]-1] = (wOut, wIn) (ctx.linCheckConstraints).  Plans and checkers are borrowed: they
+ * outlive the handle.  Every checker has the encoder plan's rank and field (RG_ERR_INVALID). */
+typedef struct rg_lincheck rg_lincheck;
+rg_status rg_buckler_lincheck_create(const rg_ntt* enc_plan, const rg_ntt* emb_plan, size_t n_chk,
+                                     const rg_linchecker* const* chk, const size_t* pair_off, const uint64_t* pairs,
+                                     rg_lincheck** out);
+void rg_buckler_lincheck_destroy(rg_lincheck* lc);
+/* d_batch_const, d_lin_const: one element each; d_mask [emb][L] (linCheckMask); d_w [n_w][emb][L] =
+ * wEcdNTT (a pair index >= n_w is RG_ERR_INVALID).  The power vector, every checker's transpose
+ * of it, one batched Encode and one batched NTT, one fused pass over the coefficients (eval =
+ * eval bc + ecdTr w[wIn] - ecd w[wOut] per pair, eval in registers), then the check tail with
+ * scale = bc and n_quo = rank: d_quo [rank][L], d_rem_lo [rank-1][L], d_rem_hi [jindo_rank][L].
+ * d_scratch holds rg_buckler_lin_check_scratch_bytes(lc) bytes; calls on different streams use
+ * different scratch.  When the call has completed, remPoly [emb][L] stands in d_scratch at byte
+ * offset rg_buckler_lin_check_rem_offset_bytes(lc): its element 0 is the sum the verifier compares
+ * with LinCheckMaskSum (verifier.go:288-293), which linCheck itself does not return. */
+size_t rg_buckler_lin_check_scratch_bytes(const rg_lincheck* lc);
+size_t rg_buckler_lin_check_rem_offset_bytes(const rg_lincheck* lc);
+rg_status rg_buckler_lin_check_dev(const rg_lincheck* lc, const uint64_t* d_batch_const, const uint64_t* d_lin_const,
+                                   const uint64_t* d_mask, const uint64_t* d_w, size_t n_w, size_t jindo_rank,
+                                   uint64_t* d_quo, uint64_t* d_rem_lo, uint64_t* d_rem_hi, uint64_t* d_scratch,
+                                   void* stream);
+rg_status rg_buckler_lin_check(const rg_lincheck* lc, const uint64_t* batch_const, const uint64_t* lin_const,
+                               const uint64_t* mask, const uint64_t* w, size_t n_w, size_t jindo_rank, uint64_t* quo,
+                               uint64_t* rem_lo, uint64_t* rem_hi);
+
 /* ------------------------------------------------------------------------------------ */
 /* Jindo commitment (jindo/params.go, encoder.go, rns.go, prover.go, entities.go)         */
 /* ------------------------------------------------------------------------------------ */

@@ -89,6 +89,40 @@ _SIGS = {
                                                    vp, vp]),
     "rg_buckler_eval_circuit": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p, ctypes.c_size_t, u64p,
                                                ctypes.c_size_t, u64p]),
+    "rg_buckler_checker_create_ntt": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_buckler_checker_create_aut": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int,
+                                                     ctypes.POINTER(vp)]),
+    "rg_buckler_checker_create_proj": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_buckler_checker_create_recompose": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, ctypes.c_size_t,
+                                                           ctypes.POINTER(vp)]),
+    "rg_buckler_checker_destroy": (None, [vp]),
+    "rg_buckler_checker_set_xof_dev": (ctypes.c_int, [vp, vp, vp]),
+    "rg_buckler_checker_set_xof": (ctypes.c_int, [vp, ctypes.c_char_p]),
+    "rg_buckler_checker_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_buckler_checker_transform_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp, vp]),
+    "rg_buckler_checker_transpose_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp]),
+    "rg_buckler_checker_transform": (ctypes.c_int, [vp, u64p, u64p]),
+    "rg_buckler_checker_transpose": (ctypes.c_int, [vp, u64p, u64p]),
+    "rg_buckler_powers_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, vp]),
+    "rg_buckler_powers": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, u64p]),
+    "rg_buckler_sumcheck_mask_dev": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp,
+                                                    vp]),
+    "rg_buckler_sumcheck_mask": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p,
+                                                u64p]),
+    "rg_buckler_check_finish_scratch_bytes": (ctypes.c_size_t, [vp]),
+    "rg_buckler_check_finish_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                                   vp, vp, vp, vp, vp]),
+    "rg_buckler_check_finish": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t,
+                                               ctypes.c_size_t, u64p, u64p, u64p]),
+    "rg_buckler_lincheck_create": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.POINTER(vp),
+                                                  ctypes.POINTER(ctypes.c_size_t), u64p, ctypes.POINTER(vp)]),
+    "rg_buckler_lincheck_destroy": (None, [vp]),
+    "rg_buckler_lin_check_scratch_bytes": (ctypes.c_size_t, [vp]),
+    "rg_buckler_lin_check_rem_offset_bytes": (ctypes.c_size_t, [vp]),
+    "rg_buckler_lin_check_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp,
+                                                vp]),
+    "rg_buckler_lin_check": (ctypes.c_int, [vp, u64p, u64p, u64p, u64p, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p,
+                                            u64p]),
     "rg_jindo_create": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), u64p, u64p, u64p, ctypes.POINTER(vp)]),
     "rg_jindo_create_from_crs": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), ctypes.c_char_p, ctypes.c_size_t,
                                                 ctypes.POINTER(vp)]),
