@@ -288,7 +288,12 @@ rg_status rg_buckler_lin_check(const rg_lincheck* lc, const uint64_t* batch_cons
 /* Jindo commitment (jindo/params.go, encoder.go, rns.go, prover.go, entities.go)         */
 /* ------------------------------------------------------------------------------------ */
 /* Shapes exactly as jindo.Parameters holds them (params.go:64-123); taken from Go
- * (NewParameters' float search is not re-derived here). */
+ * (NewParameters' float search is not re-derived here).
+ * Accepted beyond NewParameters' own shapes (tests/golden/jindo_synth_params.json runs them): any
+ * power-of-two d in 2..1024, 1..4 distinct primes q = 1 mod 2d below 2^62 per ring, of any sizes
+ * and in any order, 2 <= base < 2^32 below every ring prime, slots * exp <= d (coefficients
+ * [slots * exp, d) of an encode carry no digit), MSIS ranks up to 32.  The device samplers
+ * (rg_jindo_sample_dev, rg_jindo_commit_sampled_dev) cover d = 256 only: RG_ERR_UNSUPPORTED. */
 typedef struct {
   int rank, rows, cols, slots; /* Rank() Rows() Cols() Slots()                      */
   int exp;                     /* Exp(): digits per element (k)                      */

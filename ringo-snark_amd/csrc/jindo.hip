@@ -343,7 +343,8 @@ __global__ __launch_bounds__(256) void digits_kernel(DigitArgs<L> a) {
   out[(S.exp - 1) * S.slots + slot] = w[0];
 }
 
-// zero-fill digit slots not covered (d > exp*slots never happens for jindo; kept for safety)
+// Coefficients [slots * exp, d) of a digit polynomial belong to no slot (slots * exp < d: never a
+// NewParameters shape, but rg_jindo_create accepts it); launch_digits zeroes the buffer then.
 
 // ------------------------------------------------------------------------------------------
 // 2. prep: encode tail / MLWE finalize + NTT
@@ -834,7 +835,9 @@ __device__ __forceinline__ bool crt_centred(const CrtDev& crt, int ns, const uin
       uint64_t v = r[j];
       for (int kk = 0; kk < j; ++kk) {
         uint64_t xk = x[kk];
-        if (xk >= qj) xk = (xk - qj >= qj) ? xk % qj : xk - qj;  // ring primes share a bit size
+        // x_k < q_k must be below q_j for mod_sub: one subtraction where q_k < 2 q_j (primes of
+        // one bit size, every NewParameters ring), x_k % q_j for any other pair of primes
+        if (xk >= qj) xk = (xk - qj >= qj) ? xk % qj : xk - qj;
         v = mod_sub(v, xk, qj);
         v = sh_mul(v, crt.inv[j][kk], crt.inv_sh[j][kk], qj);
       }
@@ -2498,6 +2501,8 @@ static rg_status launch_digits(const rg_jindo* J, size_t batch, const uint64_t* 
   a.d_rows = make_idxdiv((uint32_t)J->p.rows);
   a.d_cols1 = make_idxdiv((uint32_t)(J->p.cols + 1));
   const long long blocks = (a.total + 255) / 256;
+  if (J->p.slots * J->p.exp < J->p.d)  // the coefficients no thread writes read as zero digits (baseEncodeTo)
+    RG_HIP(hipMemsetAsync(digits, 0, (size_t)batch * (J->p.cols + 1) * J->p.rows * J->p.d * sizeof(uint32_t), st));
   hipLaunchKernelGGL(digits_kernel<L>, dim3((unsigned)blocks), dim3(256), 0, st, a);
   return check_launch("jindo digits");
 }

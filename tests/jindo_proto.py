@@ -51,18 +51,22 @@ def left_right(P, F, x):
     return left, right
 
 
-def honest_proof(P, fq, ck, seed, nv=None, B=None):
+def honest_proof(P, fq, ck, seed, nv=None, B=None, rnd=None, v=None):
     """Commit B = params.batch vectors, Evaluate at a random x, return every Verify input
-    (include/ringo.h rg_jindo_verify_dev layouts) plus the openings."""
+    (include/ringo.h rg_jindo_verify_dev layouts) plus the openings.  rnd: injected randomness
+    with a leading batch dimension (make_randomness(..., batch=B)) instead of the oracle's samplers,
+    for parameter sets without sampler widths; v: the committed vectors [B][nv][L]."""
     cj = co.CJindo(P, fq)
     F = co.CField(fq)
     L = F.L
     B = B or P["batch"]
     nv = nv or P["rank"]
     rng = np.random.default_rng(seed)
-    v = np.stack([make_v(fq, nv, seed=seed * 100 + b) for b in range(B)])
+    if v is None:
+        v = np.stack([make_v(fq, nv, seed=seed * 100 + b) for b in range(B)])
     seeds = rng.bytes(192)
-    rnd = cj.sample([P[k] for k in SD_KEYS], pyref.delta_inv(P["base"], P["exp"]), seeds, 0, v)
+    if rnd is None:
+        rnd = cj.sample([P[k] for k in SD_KEYS], pyref.delta_inv(P["base"], P["exp"]), seeds, 0, v)
     opens = [cj.commit(ck[0], ck[1], ck[2], v[b], rnd["last_row"][b], rnd["mask"][b], rnd["enc_noise"][b],
                        rnd["mlwe_noise"][b]) for b in range(B)]
     com = np.stack([o["com"] for o in opens])
