@@ -284,6 +284,47 @@ rg_status rg_buckler_lin_check(const rg_lincheck* lc, const uint64_t* batch_cons
                                const uint64_t* mask, const uint64_t* w, size_t n_w, size_t jindo_rank, uint64_t* quo,
                                uint64_t* rem_lo, uint64_t* rem_hi);
 
+/* ---- Buckler norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---- */
+/* decomposeBig on the device: a Montgomery element w is taken out of Montgomery form, centred
+ * (x > q >> 1 stands for x - q) and walked down the base b_0, b_1, ...: digit +1 and x -= b_j while
+ * x >= b_j, digit -1 and x += b_j while x <= -b_j, else 0.  The digits come out as the field
+ * elements SetInt64 makes: 0, R mod q, q - (R mod q).  A value beyond the sum of the base leaves a
+ * residual, as in the reference; it is no error.
+ *
+ * The handle holds the base [nb][L] as PLAIN little-endian integers (not Montgomery; the caller
+ * computes decomposeBase(bound), utils.go:7-32) with R mod q and its negation.  An element that
+ * does not fit L limbs is given as 2^(64L) - 1: no |x| <= q / 2 reaches either.  nb = 0 or a zero
+ * base element is RG_ERR_INVALID.  Creating a handle touches no device: the base is uploaded once,
+ * by the first call that runs a kernel, to the device current then (that one call waits for the
+ * copy; capture a graph only after it).  Every `_dev` entry validates its arguments before it
+ * touches the device, writes every word of its output, and is asynchronous on `stream`; d_out ==
+ * d_w is RG_ERR_INVALID, as is any other aliasing.  rank <= 2^30, batch <= 65535. */
+typedef struct rg_dcmp rg_dcmp;
+rg_status rg_buckler_dcmp_create(const rg_field* f, const uint64_t* base, size_t nb, rg_dcmp** out);
+void rg_buckler_dcmp_destroy(rg_dcmp* h);
+/* The infinity-norm expansion (prover.go:77-86): d_w [batch][rank][L] -> d_out [batch][nb][rank][L],
+ * digit-major: d_out + (k nb + j) rank L is digit witness j of input k, so d_out is a batch of
+ * batch * nb witnesses as rg_buckler_encode_dev takes them. */
+rg_status rg_buckler_dcmp_inf_dev(const rg_dcmp* h, const uint64_t* d_w, size_t batch, size_t rank, uint64_t* d_out,
+                                  void* stream);
+/* The projection decomposition (prover.go:182-192): d_out[i nb + j] = digit j of d_w[i], i < 128;
+ * entries 128 nb .. rank - 1 are zero.  d_w holds at least 128 elements, d_out [rank][L];
+ * rank < 128 or 128 nb > rank is RG_ERR_INVALID. */
+rg_status rg_buckler_dcmp_proj_dev(const rg_dcmp* h, const uint64_t* d_w, size_t rank, uint64_t* d_out, void* stream);
+/* The two-norm witness (prover.go:99-110) of each of `batch` vectors d_w [batch][rank][L]: sqNm =
+ * sum_i plain(w_i)^2 mod q of that vector alone, then decomposeBig(sqNm) through the centring (a sum
+ * above q / 2 gives -1 digits).  d_out [batch][rank][L]: the digits in entries 0 .. nb - 1, zero
+ * above; nb > rank is RG_ERR_INVALID.  d_sq (optional) [batch][L]: sqNm in Montgomery form.  The
+ * squares are summed per workgroup into d_scratch (rg_buckler_dcmp_two_scratch_bytes bytes) and
+ * those sums in a fixed order: no atomics, and the result is exact either way. */
+size_t rg_buckler_dcmp_two_scratch_bytes(const rg_dcmp* h, size_t batch, size_t rank);
+rg_status rg_buckler_dcmp_two_dev(const rg_dcmp* h, const uint64_t* d_w, size_t batch, size_t rank, uint64_t* d_out,
+                                  uint64_t* d_sq, uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_dcmp_inf(const rg_dcmp* h, const uint64_t* w, size_t batch, size_t rank, uint64_t* out);
+rg_status rg_buckler_dcmp_proj(const rg_dcmp* h, const uint64_t* w, size_t rank, uint64_t* out);
+rg_status rg_buckler_dcmp_two(const rg_dcmp* h, const uint64_t* w, size_t batch, size_t rank, uint64_t* out,
+                              uint64_t* sq);
+
 /* ------------------------------------------------------------------------------------ */
 /* Jindo commitment (jindo/params.go, encoder.go, rns.go, prover.go, entities.go)         */
 /* ------------------------------------------------------------------------------------ */

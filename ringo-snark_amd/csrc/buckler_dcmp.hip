@@ -1,0 +1,392 @@
+// buckler_dcmp.hip -- the norm decomposition of the Buckler prover (buckler/utils.go:34-56 as used
+// at buckler/prover.go:77-86, 88-111, 182-192), for gfx950:
+//   * the infinity-norm expansion (prover.go:77-86): every coefficient of a witness into len(base)
+//     ternary digits, written digit-major so that the output is a batch of digit witnesses the
+//     Encoder takes as it stands;
+//   * the projection decomposition of the second commit round (prover.go:182-192): the first 128
+//     entries of the projected witness into 128 * len(base) digits, zero above;
+//   * the two-norm witness (prover.go:99-110): sqNm = sum of the squared coefficients mod q, then
+//     its decomposition.
+// The arithmetic is dcmp.hpp's sign-magnitude form of decomposeBig; the digits are the field
+// elements SetInt64 makes (0, R mod q, q - R mod q), so every output limb equals the reference's.
+// Every kernel writes every word of its output.
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "common.hpp"
+#include "dcmp.hpp"
+#include "field.hpp"
+#include "host_field.hpp"
+
+struct rg_dcmp {
+  rg_field f;
+  long long nb = 0;
+  std::vector<uint64_t> hbase;  // [nb][L] plain integers
+  uint64_t one[16], neg_one[16];  // SetInt64(1), SetInt64(-1)
+  // the device copy of the base, made once by the first call that runs a kernel (creating a
+  // handle touches no device)
+  mutable std::mutex mu;
+  mutable bool uploaded = false;
+  mutable rg::DevBuf base;
+};
+
+namespace rg {
+
+constexpr int kDcmpProjRows = 128;  // prover.go:185
+constexpr int kTwoBlock = 256;
+constexpr int kTwoChunk = 1024;  // coefficients per workgroup of the sum of squares
+
+template <int L>
+struct DcmpConst {
+  FieldParams<L> F;
+  uint64_t one[L], neg_one[L];
+};
+
+template <int L>
+__device__ __forceinline__ void load_el(uint64_t* d, const uint64_t* s) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) d[l] = s[l];
+}
+
+// ---- prover.go:77-86: a lane per coefficient, grid (rank blocks, batch) ---------------------
+// The base index j is uniform, so base[j] comes through scalar loads.  For fixed j consecutive
+// lanes store consecutive elements of digit witness j; the L words of an element leave as 16-byte
+// stores (the compiler pairs them: global_store_dwordx4, L = 7 ends on one dwordx2).
+template <int L>
+__global__ __launch_bounds__(256) void dcmp_inf_kernel(DcmpConst<L> K, uint64_t* __restrict__ out,
+                                                       const uint64_t* __restrict__ w,
+                                                       const uint64_t* __restrict__ base, long long nb,
+                                                       long long rank) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rank) return;
+  const long long k = blockIdx.y;
+  uint64_t x[L], c[L];
+  load_el<L>(x, w + (k * rank + i) * L);
+  Dcmp<L> d;
+  dcmp_init<L>(d, x, K.F);
+  dcmp_unit<L>(c, d, K.one, K.neg_one);
+  uint64_t* o = out + (k * nb * rank + i) * L;
+  for (long long j = 0; j < nb; ++j) {
+    uint64_t b[L], v[L];
+    load_el<L>(b, base + j * L);
+    const uint64_t mask = 0 - (uint64_t)dcmp_step<L>(d, b);
+#pragma unroll
+    for (int l = 0; l < L; ++l) v[l] = c[l] & mask;
+#pragma unroll
+    for (int l = 0; l < L; ++l) o[l] = v[l];
+    o += rank * L;
+  }
+}
+
+// ---- prover.go:182-192: lane t < 128 decomposes coefficient t into out[t nb .. t nb + nb - 1];
+// lane t >= 128 nb writes the zero at t.  128 nb <= rank, so every entry has one writer.
+template <int L>
+__global__ __launch_bounds__(256) void dcmp_proj_kernel(DcmpConst<L> K, uint64_t* __restrict__ out,
+                                                        const uint64_t* __restrict__ w,
+                                                        const uint64_t* __restrict__ base, long long nb,
+                                                        long long rank) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= rank) return;
+  if (t >= kDcmpProjRows * nb) {
+#pragma unroll
+    for (int l = 0; l < L; ++l) out[t * L + l] = 0;
+  }
+  if (t >= kDcmpProjRows) return;
+  uint64_t x[L], c[L];
+  load_el<L>(x, w + t * L);
+  Dcmp<L> d;
+  dcmp_init<L>(d, x, K.F);
+  dcmp_unit<L>(c, d, K.one, K.neg_one);
+  uint64_t* o = out + t * nb * L;
+  for (long long j = 0; j < nb; ++j) {
+    uint64_t b[L];
+    load_el<L>(b, base + j * L);
+    const uint64_t mask = 0 - (uint64_t)dcmp_step<L>(d, b);
+#pragma unroll
+    for (int l = 0; l < L; ++l) o[j * L + l] = c[l] & mask;
+  }
+}
+
+// ---- prover.go:99-104, stage 1: the squares of one chunk of coefficients summed per workgroup.
+// f_mul(w, w) is the Montgomery form of plain(w)^2, and f_add keeps canonical residues, so the
+// sum is exact whatever the order.  partial [batch][chunks][L].
+template <int L>
+__global__ __launch_bounds__(kTwoBlock) void dcmp_two_partial_kernel(FieldParams<L> F, uint64_t* __restrict__ partial,
+                                                                     const uint64_t* __restrict__ w,
+                                                                     long long rank) {
+  __shared__ uint64_t red[kTwoBlock * L];
+  const int tid = threadIdx.x;
+  const long long k = blockIdx.y, i0 = (long long)blockIdx.x * kTwoChunk;
+  uint64_t acc[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) acc[l] = 0;
+#pragma unroll 1
+  for (int r = 0; r < kTwoChunk / kTwoBlock; ++r) {
+    const long long i = i0 + r * kTwoBlock + tid;
+    if (i < rank) {
+      uint64_t x[L];
+      load_el<L>(x, w + (k * rank + i) * L);
+      f_mul<L>(x, x, x, F);
+      f_add<L>(acc, acc, x, F);
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < L; ++l) red[tid * L + l] = acc[l];
+  __syncthreads();
+#pragma unroll 1
+  for (int h = kTwoBlock / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      uint64_t y[L];
+      load_el<L>(y, red + (tid + h) * L);
+      f_add<L>(acc, acc, y, F);
+#pragma unroll
+      for (int l = 0; l < L; ++l) red[tid * L + l] = acc[l];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int l = 0; l < L; ++l) partial[(k * gridDim.x + blockIdx.x) * L + l] = acc[l];
+  }
+}
+
+// stage 2 (prover.go:104-110): a lane per output entry.  A workgroup whose entries reach below nb
+// sums the partials in chunk order and walks the base; every lane does so on the same values (the
+// loads are uniform), and lane i keeps the digit of step i.  The other workgroups write zeros.
+template <int L>
+__global__ __launch_bounds__(256) void dcmp_two_final_kernel(DcmpConst<L> K, uint64_t* __restrict__ out,
+                                                             uint64_t* __restrict__ sq,
+                                                             const uint64_t* __restrict__ partial,
+                                                             const uint64_t* __restrict__ base, long long nb,
+                                                             long long rank, long long chunks) {
+  const long long i0 = (long long)blockIdx.x * blockDim.x, i = i0 + threadIdx.x;
+  const long long k = blockIdx.y;
+  uint64_t v[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) v[l] = 0;
+  if (i0 < nb) {
+    uint64_t acc[L], c[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) acc[l] = 0;
+    for (long long ch = 0; ch < chunks; ++ch) {
+      uint64_t y[L];
+      load_el<L>(y, partial + (k * chunks + ch) * L);
+      f_add<L>(acc, acc, y, K.F);
+    }
+    if (sq && i == 0) {
+#pragma unroll
+      for (int l = 0; l < L; ++l) sq[k * L + l] = acc[l];
+    }
+    Dcmp<L> d;
+    dcmp_init<L>(d, acc, K.F);
+    dcmp_unit<L>(c, d, K.one, K.neg_one);
+    const long long j1 = min(nb, i0 + (long long)blockDim.x);
+    for (long long j = 0; j < j1; ++j) {
+      uint64_t b[L];
+      load_el<L>(b, base + j * L);
+      const uint64_t mask = 0 - (uint64_t)(dcmp_step<L>(d, b) && j == i);
+#pragma unroll
+      for (int l = 0; l < L; ++l) v[l] |= c[l] & mask;
+    }
+  }
+  if (i >= rank) return;
+#pragma unroll
+  for (int l = 0; l < L; ++l) out[(k * rank + i) * L + l] = v[l];
+}
+
+// ---- host side ----------------------------------------------------------------------------------
+template <int L>
+static DcmpConst<L> consts(const rg_dcmp* h) {
+  DcmpConst<L> K;
+  memcpy(K.F.q, h->f.q, 8 * L);
+  K.F.qinv = h->f.qinv;
+  memcpy(K.one, h->one, 8 * L);
+  memcpy(K.neg_one, h->neg_one, 8 * L);
+  return K;
+}
+
+static unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
+static bool dcmp_supported_L(int L) { return L == 1 || L == 2 || L == 4 || L == 7 || L == 14; }
+static long long two_chunks(long long rank) { return (rank + kTwoChunk - 1) / kTwoChunk; }
+
+constexpr size_t kMaxRank = (size_t)1 << 30;
+constexpr size_t kMaxBatch = 65535;  // the batch is the grid's y extent
+
+// the base on the device; the first caller uploads it and every later one finds it there
+static rg_status ensure_base(const rg_dcmp* h) {
+  std::lock_guard<std::mutex> lock(h->mu);
+  if (h->uploaded) return RG_OK;
+  RG_TRY(h->base.upload(h->hbase.data(), h->hbase.size() * 8));
+  h->uploaded = true;
+  return RG_OK;
+}
+
+template <int L>
+static rg_status inf_L(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(dcmp_inf_kernel<L>, dim3(blocks256(rank), (unsigned)batch), dim3(256), 0, st, consts<L>(h), out, w,
+                     h->base.as<uint64_t>(), h->nb, rank);
+  return check_launch("dcmp inf");
+}
+
+template <int L>
+static rg_status proj_L(const rg_dcmp* h, const uint64_t* w, long long rank, uint64_t* out, hipStream_t st) {
+  hipLaunchKernelGGL(dcmp_proj_kernel<L>, dim3(blocks256(rank)), dim3(256), 0, st, consts<L>(h), out, w,
+                     h->base.as<uint64_t>(), h->nb, rank);
+  return check_launch("dcmp proj");
+}
+
+template <int L>
+static rg_status two_L(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
+                       uint64_t* sq, uint64_t* scratch, hipStream_t st) {
+  const long long chunks = two_chunks(rank);
+  const DcmpConst<L> K = consts<L>(h);
+  hipLaunchKernelGGL(dcmp_two_partial_kernel<L>, dim3((unsigned)chunks, (unsigned)batch), dim3(kTwoBlock), 0, st, K.F,
+                     scratch, w, rank);
+  RG_TRY(check_launch("dcmp two-norm squares"));
+  hipLaunchKernelGGL(dcmp_two_final_kernel<L>, dim3(blocks256(rank), (unsigned)batch), dim3(256), 0, st, K, out, sq,
+                     scratch, h->base.as<uint64_t>(), h->nb, rank, chunks);
+  return check_launch("dcmp two-norm digits");
+}
+
+#define RG_DCMP_DISPATCH(L_, CALL)      \
+  switch (L_) {                         \
+    case 1: return CALL(1);             \
+    case 2: return CALL(2);             \
+    case 4: return CALL(4);             \
+    case 7: return CALL(7);             \
+    case 14: return CALL(14);           \
+    default: return RG_ERR_UNSUPPORTED; \
+  }
+
+static rg_status launch_inf(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
+                            hipStream_t st) {
+#define RG_CALL(L) inf_L<L>(h, w, batch, rank, out, st)
+  RG_DCMP_DISPATCH(h->f.L, RG_CALL)
+#undef RG_CALL
+}
+static rg_status launch_proj(const rg_dcmp* h, const uint64_t* w, long long rank, uint64_t* out, hipStream_t st) {
+#define RG_CALL(L) proj_L<L>(h, w, rank, out, st)
+  RG_DCMP_DISPATCH(h->f.L, RG_CALL)
+#undef RG_CALL
+}
+static rg_status launch_two(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
+                            uint64_t* sq, uint64_t* scratch, hipStream_t st) {
+#define RG_CALL(L) two_L<L>(h, w, batch, rank, out, sq, scratch, st)
+  RG_DCMP_DISPATCH(h->f.L, RG_CALL)
+#undef RG_CALL
+}
+
+static bool inf_args_ok(const rg_dcmp* h, const void* w, size_t batch, size_t rank, const void* out) {
+  return h && w && out && out != w && rank >= 1 && rank <= kMaxRank && batch <= kMaxBatch;
+}
+static bool proj_args_ok(const rg_dcmp* h, const void* w, size_t rank, const void* out) {
+  return h && w && out && out != w && rank >= (size_t)kDcmpProjRows && rank <= kMaxRank &&
+         (size_t)h->nb <= rank / kDcmpProjRows;
+}
+static bool two_args_ok(const rg_dcmp* h, const void* w, size_t batch, size_t rank, const void* out) {
+  return h && w && out && out != w && rank >= 1 && rank <= kMaxRank && batch <= kMaxBatch && (size_t)h->nb <= rank;
+}
+
+}  // namespace rg
+
+using namespace rg;
+
+extern "C" {
+
+rg_status rg_buckler_dcmp_create(const rg_field* f, const uint64_t* base, size_t nb, rg_dcmp** out) {
+  if (!f || !out) return RG_ERR_INVALID;
+  *out = nullptr;
+  if (!base || nb == 0 || nb > kMaxRank) return RG_ERR_INVALID;
+  if (!dcmp_supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  const int L = f->L;
+  for (size_t j = 0; j < nb; ++j) {  // b_j >= 1 (dcmp.hpp)
+    uint64_t orv = 0;
+    for (int l = 0; l < L; ++l) orv |= base[j * L + l];
+    if (!orv) return RG_ERR_INVALID;
+  }
+  auto h = new rg_dcmp();
+  h->f = *f;
+  h->nb = (long long)nb;
+  h->hbase.assign(base, base + nb * L);
+  memset(h->one, 0, sizeof(h->one));
+  memset(h->neg_one, 0, sizeof(h->neg_one));
+  memcpy(h->one, f->one, 8 * L);
+  HostField::sub_n(h->neg_one, f->q, f->one, L);  // R mod q is in [1, q): q - R mod q is canonical
+  *out = h;
+  return RG_OK;
+}
+
+void rg_buckler_dcmp_destroy(rg_dcmp* h) { delete h; }
+
+rg_status rg_buckler_dcmp_inf_dev(const rg_dcmp* h, const uint64_t* d_w, size_t batch, size_t rank, uint64_t* d_out,
+                                  void* stream) {
+  if (!inf_args_ok(h, d_w, batch, rank, d_out)) return RG_ERR_INVALID;
+  if (batch == 0) return RG_OK;
+  RG_TRY(ensure_base(h));
+  return launch_inf(h, d_w, (long long)batch, (long long)rank, d_out, as_stream(stream));
+}
+
+rg_status rg_buckler_dcmp_proj_dev(const rg_dcmp* h, const uint64_t* d_w, size_t rank, uint64_t* d_out, void* stream) {
+  if (!proj_args_ok(h, d_w, rank, d_out)) return RG_ERR_INVALID;
+  RG_TRY(ensure_base(h));
+  return launch_proj(h, d_w, (long long)rank, d_out, as_stream(stream));
+}
+
+size_t rg_buckler_dcmp_two_scratch_bytes(const rg_dcmp* h, size_t batch, size_t rank) {
+  if (!h) return 0;
+  return batch * (size_t)two_chunks((long long)rank) * h->f.L * 8;
+}
+
+rg_status rg_buckler_dcmp_two_dev(const rg_dcmp* h, const uint64_t* d_w, size_t batch, size_t rank, uint64_t* d_out,
+                                  uint64_t* d_sq, uint64_t* d_scratch, void* stream) {
+  if (!two_args_ok(h, d_w, batch, rank, d_out) || !d_scratch) return RG_ERR_INVALID;
+  if (d_scratch == d_w || d_scratch == d_out || (d_sq && (d_sq == d_w || d_sq == d_out || d_sq == d_scratch)))
+    return RG_ERR_INVALID;
+  if (batch == 0) return RG_OK;
+  RG_TRY(ensure_base(h));
+  return launch_two(h, d_w, (long long)batch, (long long)rank, d_out, d_sq, d_scratch, as_stream(stream));
+}
+
+rg_status rg_buckler_dcmp_inf(const rg_dcmp* h, const uint64_t* w, size_t batch, size_t rank, uint64_t* out) {
+  if (!inf_args_ok(h, w, batch, rank, out)) return RG_ERR_INVALID;
+  if (batch == 0) return RG_OK;
+  const size_t in_bytes = batch * rank * h->f.L * 8, out_bytes = in_bytes * (size_t)h->nb;
+  DevBuf dw, dout;
+  RG_TRY(dw.upload(w, in_bytes));
+  RG_TRY(dout.alloc(out_bytes));
+  RG_TRY(rg_buckler_dcmp_inf_dev(h, dw.as<uint64_t>(), batch, rank, dout.as<uint64_t>(), nullptr));
+  RG_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  return RG_OK;
+}
+
+rg_status rg_buckler_dcmp_proj(const rg_dcmp* h, const uint64_t* w, size_t rank, uint64_t* out) {
+  if (!proj_args_ok(h, w, rank, out)) return RG_ERR_INVALID;
+  const size_t e = h->f.L * 8;
+  DevBuf dw, dout;
+  RG_TRY(dw.upload(w, kDcmpProjRows * e));  // only w[0..127] is read
+  RG_TRY(dout.alloc(rank * e));
+  RG_TRY(rg_buckler_dcmp_proj_dev(h, dw.as<uint64_t>(), rank, dout.as<uint64_t>(), nullptr));
+  RG_HIP(hipMemcpy(out, dout.p, rank * e, hipMemcpyDeviceToHost));
+  return RG_OK;
+}
+
+rg_status rg_buckler_dcmp_two(const rg_dcmp* h, const uint64_t* w, size_t batch, size_t rank, uint64_t* out,
+                              uint64_t* sq) {
+  if (!two_args_ok(h, w, batch, rank, out) || (sq && (sq == w || sq == out))) return RG_ERR_INVALID;
+  if (batch == 0) return RG_OK;
+  const size_t e = h->f.L * 8;
+  DevBuf dw, dout, dsq, dscr;
+  RG_TRY(dw.upload(w, batch * rank * e));
+  RG_TRY(dout.alloc(batch * rank * e));
+  RG_TRY(dsq.alloc(batch * e));
+  RG_TRY(dscr.alloc(rg_buckler_dcmp_two_scratch_bytes(h, batch, rank)));
+  RG_TRY(rg_buckler_dcmp_two_dev(h, dw.as<uint64_t>(), batch, rank, dout.as<uint64_t>(), dsq.as<uint64_t>(),
+                                 dscr.as<uint64_t>(), nullptr));
+  RG_HIP(hipMemcpy(out, dout.p, batch * rank * e, hipMemcpyDeviceToHost));
+  if (sq) RG_HIP(hipMemcpy(sq, dsq.p, batch * e, hipMemcpyDeviceToHost));
+  return RG_OK;
+}
+
+}  // extern "C"

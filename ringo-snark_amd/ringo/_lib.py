@@ -123,6 +123,15 @@ _SIGS = {
                                                 vp]),
     "rg_buckler_lin_check": (ctypes.c_int, [vp, u64p, u64p, u64p, u64p, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p,
                                             u64p]),
+    "rg_buckler_dcmp_create": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_buckler_dcmp_destroy": (None, [vp]),
+    "rg_buckler_dcmp_inf_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),
+    "rg_buckler_dcmp_proj_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, vp]),
+    "rg_buckler_dcmp_two_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t, ctypes.c_size_t]),
+    "rg_buckler_dcmp_two_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]),
+    "rg_buckler_dcmp_inf": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.c_size_t, u64p]),
+    "rg_buckler_dcmp_proj": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, u64p]),
+    "rg_buckler_dcmp_two": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p]),
     "rg_jindo_create": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), u64p, u64p, u64p, ctypes.POINTER(vp)]),
     "rg_jindo_create_from_crs": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), ctypes.c_char_p, ctypes.c_size_t,
                                                 ctypes.POINTER(vp)]),

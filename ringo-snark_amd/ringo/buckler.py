@@ -15,6 +15,14 @@ sumCheckMask, and linCheck / sumCheck / arithCheck with their challenges injecte
     proj = ProjChecker(F, rank); proj.SetXOF(xof_bytes)        # prover.go:168-176
     mask, maskSum = SumCheckMask(F, rank, maskRank, embRank, rand)
     quo, remLo, remHi = LinCheck(F, rank, embRank, jindoRank, bc, lc, mask, checkers, pairs, wEcdNTT)
+
+and the norm decomposition of the witness assignment (buckler/utils.go:34-56, prover.go:77-111,
+182-192):
+
+    dc = Decomposer(F, bound)                                  # decomposeBase(bound) uploaded once
+    digits = dc.DecomposeInf(w)                                # [nb][rank][L], one witness per digit
+    wDcmp = dc.DecomposeProj(wProj)                            # second round, prover.go:182-192
+    wDcmp, sqNm = dc.DecomposeTwoNorm(w); pwBase, pwMask = TwoNormPublic(F, rank, bound)
 """
 import ctypes
 
@@ -485,3 +493,125 @@ def ArithCheck(field, rank, embRank, arithCheckMaxRank, batchConst, constraints,
         raise RingoPanic("inconsistent input(s)")
     return _finish(field, NewCyclicTransformer(field, embRank), rank, ev, None, None, arithCheckMaxRank - rank, 0,
                    False)
+
+
+# ---- norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---------------
+def decomposeBig(x, base, q):
+    """decomposeBig (utils.go:34-56) on Python ints: x in [0, q) -> len(base) digits in {-1, 0, 1}."""
+    xSigned = int(x)
+    if xSigned > (q >> 1):
+        xSigned -= q
+    dcmpOut = [0] * len(base)
+    for i, b in enumerate(base):
+        if xSigned >= b:
+            dcmpOut[i] = 1
+            xSigned -= b
+        elif xSigned <= -b:
+            dcmpOut[i] = -1
+            xSigned += b
+    return dcmpOut
+
+
+class Decomposer:
+    """decomposeBig over an rg_dcmp handle: `bound_or_base` is a bound (an int: the base is
+    decomposeBase(bound)) or the base itself (a sequence of positive ints).  Witnesses are [rank][L]
+    arrays of Montgomery elements; the digits come back as field elements (SetInt64)."""
+
+    def __init__(self, field, bound_or_base):
+        self.field = field
+        self.dcmpBase = decomposeBase(bound_or_base) if isinstance(bound_or_base, int) else [int(b) for b in
+                                                                                             bound_or_base]
+        if not self.dcmpBase or min(self.dcmpBase) < 1:
+            raise RingoPanic("inconsistent input(s)")
+        # |x| <= q / 2 < 2^(64L) - 1, so a base element of 2^(64L) or more is never reached: it is
+        # stored saturated to 2^(64L) - 1, which is never reached either; the digits are unchanged
+        top = (1 << (64 * field.L)) - 1
+        base = np.ascontiguousarray(field.to_limbs([min(b, top) for b in self.dcmpBase]))
+        h = vp()
+        _status(lib().rg_buckler_dcmp_create(field.h, ptr(base), len(self.dcmpBase), ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_buckler_dcmp_destroy(self.h)
+            self.h = None
+
+    def _vec(self, w, ndim):
+        w = np.ascontiguousarray(np.asarray(w, np.uint64))
+        if w.ndim != ndim or w.shape[-1] != self.field.L:
+            raise RingoPanic("inconsistent input(s)")
+        return w
+
+    def DecomposeInf(self, w):
+        """prover.go:77-86: w [rank][L] -> [nb][rank][L], digit witness j at index j (or
+        [batch][rank][L] -> [batch][nb][rank][L])."""
+        w = np.asarray(w, np.uint64)
+        single = w.ndim == 2
+        w = self._vec(w[None] if single else w, 3)
+        batch, rank, L = w.shape
+        out = np.zeros((batch, len(self.dcmpBase), rank, L), np.uint64)
+        _status(lib().rg_buckler_dcmp_inf(self.h, ptr(w), batch, rank, ptr(out)))
+        return out[0] if single else out
+
+    def DecomposeProj(self, w):
+        """prover.go:182-192: w [rank][L] (the projected witness) -> [rank][L] with digit j of w[i],
+        i < 128, at i nb + j and zeros from 128 nb."""
+        w = self._vec(w, 2)
+        rank = w.shape[0]
+        if rank < 128 or 128 * len(self.dcmpBase) > rank:
+            raise RingoPanic("index out of range")
+        out = np.zeros((rank, self.field.L), np.uint64)
+        _status(lib().rg_buckler_dcmp_proj(self.h, ptr(w), rank, ptr(out)))
+        return out
+
+    def DecomposeTwoNorm(self, w):
+        """prover.go:99-110: w [rank][L] -> (digits [rank][L] with the nb digits of sqNm first and
+        zeros after, sqNm [L] in Montgomery form); [batch][rank][L] -> ([batch][rank][L], [batch][L])."""
+        w = np.asarray(w, np.uint64)
+        single = w.ndim == 2
+        w = self._vec(w[None] if single else w, 3)
+        batch, rank, L = w.shape
+        if len(self.dcmpBase) > rank:
+            raise RingoPanic("index out of range")
+        out = np.zeros((batch, rank, L), np.uint64)
+        sq = np.zeros((batch, L), np.uint64)
+        _status(lib().rg_buckler_dcmp_two(self.h, ptr(w), batch, rank, ptr(out), ptr(sq)))
+        return (out[0], sq[0]) if single else (out, sq)
+
+    def scratch_bytes(self, batch, rank):
+        return lib().rg_buckler_dcmp_two_scratch_bytes(self.h, batch, rank)
+
+    def inf_dev(self, d_out, d_w, batch, rank, stream=None):
+        """rg_buckler_dcmp_inf_dev: [batch][rank][L] -> [batch][nb][rank][L]."""
+        n = batch * rank * self.field.L
+        _status(lib().rg_buckler_dcmp_inf_dev(self.h, _addr(d_w, n), batch, rank,
+                                              _addr(d_out, n * len(self.dcmpBase)), _stream(stream)))
+
+    def proj_dev(self, d_out, d_w, rank, stream=None):
+        """rg_buckler_dcmp_proj_dev: d_w (at least 128 elements) -> d_out [rank][L]."""
+        L = self.field.L
+        _status(lib().rg_buckler_dcmp_proj_dev(self.h, _addr(d_w, 128 * L), rank, _addr(d_out, rank * L),
+                                               _stream(stream)))
+
+    def two_dev(self, d_out, d_w, batch, rank, d_sq=None, d_scratch=None, stream=None):
+        """rg_buckler_dcmp_two_dev: [batch][rank][L] -> d_out [batch][rank][L], d_sq [batch][L]."""
+        L = self.field.L
+        n = batch * rank * L
+        _status(lib().rg_buckler_dcmp_two_dev(
+            self.h, _addr(d_w, n), batch, rank, _addr(d_out, n), _addr(d_sq, batch * L) if d_sq is not None else None,
+            _addr(d_scratch, self.scratch_bytes(batch, rank) // 8) if d_scratch is not None else None,
+            _stream(stream)))
+
+
+def TwoNormPublic(field, rank, bound):
+    """The public witnesses of a two-norm bound (prover.go:92-97): (pwBase, pwMask), [rank][L] each,
+    with pwBase[i] = SetBigInt(base[i]) and pwMask[i] = SetInt64(1) for i < len(base), zero above."""
+    base = decomposeBase(bound)
+    if len(base) > rank:
+        raise RingoPanic("index out of range")
+    pwBase = np.zeros((rank, field.L), np.uint64)
+    pwMask = np.zeros((rank, field.L), np.uint64)
+    pwBase[:len(base)] = field.mont(base)
+    pwMask[:len(base)] = field.mont([1] * len(base))
+    return pwBase, pwMask
