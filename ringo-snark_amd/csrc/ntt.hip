@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "host_field.hpp"
+#include "ntt64.hpp"
 
 #include "ntt_plan.hpp"
 
@@ -28,8 +29,10 @@ struct rg_ntt {
   bool halving = true;  // wide fields: rank_inv == N^-1 (finalize)
   std::vector<uint64_t> h_tw, h_twinv, h_ninv;  // Montgomery reps, [N][L]
   rg::DevBuf d_tw, d_twinv;                     // kernel format
+  rg::DevBuf d_tw_mont, d_twinv_mont;           // L = 1, 2^16, ntt64_mont_ok: single Montgomery words (ntt64.hpp MONT)
   std::vector<rg::PassDesc> passes;             // forward order
   uint64_t nsc[16], nsc_sh, w1n[16], w1n_sh;
+  uint64_t nsc_mont = 0, w1n_mont = 0;  // N^-1 and twInv[1] N^-1 in Montgomery form (with d_tw_mont)
   std::unique_ptr<rg::Aux> aux;  // L = 4: helper stream of ntt256_run's split (ntt_l4_fast.hip)
   int device = 0;                // the tables and the helper stream live on this device
 };
@@ -168,26 +171,35 @@ static rg_status finalize(rg_ntt* t) {
       b[2 * i] = wi;
       b[2 * i + 1] = h_shoup(wi, q);
     }
-    if (t->logN == 16) {  // lane-ordered ROW last-round copy for ntt16_pass (ntt64.hpp)
-      auto add_row_copy = [&](std::vector<uint64_t>& v) {
+    if (t->logN == 16) {  // lane-ordered ROW last-round copy for ntt16_pass (ntt64.hpp), W words per entry
+      auto add_row_copy = [&](std::vector<uint64_t>& v, size_t W) {
         const size_t base = v.size();
-        v.resize(base + (size_t)2 * 256 * 192);
+        v.resize(base + W * 256 * 192);
         for (int r = 0; r < 256; ++r)
           for (int tt = 0; tt < 32; ++tt) {
             for (int g = 0; g < 2; ++g) {
               const size_t src = (size_t)(1 << 14) + 64 * r + 2 * tt + g, dst = (size_t)r * 192 + 32 * g + tt;
-              v[base + 2 * dst] = v[2 * src];
-              v[base + 2 * dst + 1] = v[2 * src + 1];
+              for (size_t c = 0; c < W; ++c) v[base + W * dst + c] = v[W * src + c];
             }
             for (int j = 0; j < 4; ++j) {
               const size_t src = (size_t)(1 << 15) + 128 * r + 4 * tt + j, dst = (size_t)r * 192 + 64 + 32 * j + tt;
-              v[base + 2 * dst] = v[2 * src];
-              v[base + 2 * dst + 1] = v[2 * src + 1];
+              for (size_t c = 0; c < W; ++c) v[base + W * dst + c] = v[W * src + c];
             }
           }
       };
-      add_row_copy(a);
-      add_row_copy(b);
+      add_row_copy(a, 2);
+      add_row_copy(b, 2);
+      // The Montgomery-product kernels read the reference's own representation, one word per
+      // twiddle.  The Shoup tables above stay: the generic kernels read them.
+      if (ntt64_mont_ok(q)) {
+        std::vector<uint64_t> am(t->h_tw.begin(), t->h_tw.begin() + N), bm(t->h_twinv.begin(), t->h_twinv.begin() + N);
+        add_row_copy(am, 1);
+        add_row_copy(bm, 1);
+        RG_TRY(t->d_tw_mont.upload(am.data(), am.size() * 8));
+        RG_TRY(t->d_twinv_mont.upload(bm.data(), bm.size() * 8));
+        t->nsc_mont = t->h_ninv[0];
+        t->w1n_mont = w1n[0];
+      }
     }
     RG_TRY(t->d_tw.upload(a.data(), a.size() * 8));
     RG_TRY(t->d_twinv.upload(b.data(), b.size() * 8));
@@ -257,6 +269,9 @@ static rg_status run(const rg_ntt* t, uint64_t* out, const uint64_t* in, size_t 
   p.nsc_sh = t->nsc_sh;
   p.w1n = t->w1n;
   p.w1n_sh = t->w1n_sh;
+  p.tw_mont = inv ? t->d_twinv_mont.as<uint64_t>() : t->d_tw_mont.as<uint64_t>();
+  p.nsc_mont = t->nsc_mont;
+  p.w1n_mont = t->w1n_mont;
   p.logN = t->logN;
   p.shoup = t->shoup;
   p.inv = inv;

@@ -14,10 +14,15 @@
 // Cost model (tools/ubench, MI355X): 32-bit multiplies, 64-bit shifts/adds and carry ops issue
 // at ~4.4 cycles per wave64 instruction, plain v_add/v_sub/v_and/v_mov at ~2.4; a butterfly is
 // 8 multiplies + ~13 adds/selects.
+// Moduli with q / 2^64 <= 0.2808 (ntt64_mont_ok: the config-2 prime 47104^4 + 1) take the
+// Montgomery product below instead (the MONT kernels): 6 multiplies + 3 borrow ops on single-word
+// twiddles in the reference's own Montgomery form, 19 (forward) / 20 (inverse) half-rate ops per
+// butterfly against 23.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "field.hpp"
 
@@ -36,6 +41,40 @@ RG_HD Q64 make_q64(uint64_t q) {
   Q.qhi = (uint32_t)(q >> 32);
   Q.qlo1 = (uint32_t)q == 1u;
   return Q;
+}
+
+// ---- Montgomery twiddle product with a subtractive REDC (the lazy 2^16 passes, MONT) ----
+// q = q1 2^32 + 1, y in [0, 2q), w < q a twiddle in Montgomery form (w' 2^64 mod q, the form the
+// reference's tables already have).  T = y w + 2^64 + (q - 1) 2^64 = y w + q 2^64 (the two
+// constants ride in the high words of the addends of p1 and p3: they add q to the result and keep
+// it positive), T0, T1 its low words.  q == 1 (mod 2^32) makes
+// -q^-1 == -1 (mod 2^32), so REDC's two quotient words are m0 = T0 and m1 = T1 - lo(T0 q1), and
+//   t = (T - T0 q - m1 q 2^32) / 2^64      (exact: both low words cancel)
+//     = p3 - W - b1,   Z = T0 q1,  W = m1 q1 + hi(Z),  b1 = borrow of T1 - lo(Z),
+// because T0 q = T0 + Z 2^32 and m1 q 2^32 = m1 2^32 + m1 q1 2^64: word 0 is T0 - T0 = 0, word 1
+// is T1 - lo(Z) - m1 = 0 with borrow b1 into word 2, and hi(Z) joins m1 q1 in W.
+// Result: t == y w 2^-64 (mod q) and, as T0 q + m1 q 2^32 < q 2^64,
+//   0 < t < q + ceil(2 q^2 / 2^64)                      (1.534 q for q = 47104^4 + 1).
+// No 64-bit intermediate overflows, and the forward butterfly's x + t (x < 2q) fits 64 bits,
+// when 3q + ceil(2 q^2 / 2^64) + 2^33 < 2^64: p2 = y0 w1 + y1 w0 + hi(p0) + 2^32 < 3q + 2^33,
+// p3 < y1 w1 + 2^32 + q < 2q^2/2^64 + q + 2^33, x + t < 3q + ceil(2 q^2 / 2^64).  That is
+// q1 <= 0x47e0f66a (q / 2^64 <= 0.28078), ntt64_mont_ok below; tests/test_mont64_host.py checks
+// the constant against the inequality and the product against integers at both ends.
+constexpr uint32_t kMontMaxQ1 = 0x47e0f66au;
+RG_HD bool ntt64_mont_ok(uint64_t q) { return (uint32_t)q == 1u && (q >> 32) != 0 && (q >> 32) <= kMontMaxQ1; }
+
+// portable form (host tables, tests); the device kernels use mont_x below
+RG_HD uint64_t mont64(uint64_t y, uint64_t w, uint32_t q1) {
+  const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32), w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32);
+  const uint64_t p0 = (uint64_t)y0 * w0;
+  const uint64_t p1 = (uint64_t)y0 * w1 + ((p0 >> 32) | (1ull << 32));
+  const uint64_t p2 = (uint64_t)y1 * w0 + p1;
+  const uint64_t p3 = (uint64_t)y1 * w1 + ((p2 >> 32) | ((uint64_t)q1 << 32));
+  const uint64_t Z = (uint64_t)(uint32_t)p0 * q1;
+  const uint32_t m1 = (uint32_t)p2 - (uint32_t)Z;
+  const uint64_t b1 = (uint32_t)p2 < (uint32_t)Z;
+  const uint64_t W = (uint64_t)m1 * q1 + (Z >> 32);
+  return p3 - W - b1;
 }
 
 #if defined(__HIPCC__)
@@ -186,6 +225,94 @@ __device__ __forceinline__ void inv_bfly_x(uint64_t& x, uint64_t& y, uint64_t w,
   x = pk(sel(m, u0, s0), sel(m, u1, s1));
   y = shoup_x(pk(sel(e2, lo32(f), d0), sel(e2, hi32(f), d1)), w, wp, nqhi);
 }
+// ---- Montgomery product (derivation and bounds at the top of the file): 6 multiplies and
+// 3 borrow ops, no quotient word.  The three addends {hi(p0), 1}, {hi(p2), q1}, {hi(Z), 0} are
+// 64-bit register pairs whose high word never changes.  MontK keeps one such pair per addend
+// alive for the whole tile and mont_x only rewrites its low word (one v_mov each): built afresh,
+// each pair costs two moves, which spends what the shorter product saves.  mont_k hides the pairs
+// behind an empty asm so the compiler cannot see (and rematerialise) the constant halves.  The asm
+// is not volatile: a volatile one counts as a possible store, after which the H round's uniform
+// twiddle loads are no longer provably unclobbered and turn from scalar loads into vector ones.
+struct MontK {
+  uint64_t c1, cq, c0;  // high words 1, q1, 0; low words scratch
+  uint32_t q1;
+};
+__device__ __forceinline__ MontK mont_k(uint32_t q1) {
+  MontK K;
+  K.c1 = 1ull << 32;
+  K.cq = (uint64_t)q1 << 32;
+  K.c0 = 0;
+  K.q1 = q1;
+  asm("" : "+v"(K.c1), "+v"(K.cq), "+v"(K.c0));
+  return K;
+}
+// (lo, hi) as one register pair the compiler cannot take apart again: a 64-bit add of pk(lo, hi)
+// is otherwise split into an add of {lo, 0} and a 32-bit add of hi (two more full-rate ops)
+__device__ __forceinline__ uint64_t pair(uint32_t lo, uint32_t hi) {
+  uint64_t v = pk(lo, hi);
+  asm("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ uint64_t with_lo(uint64_t v, uint32_t lo) { return (v & 0xffffffff00000000ull) | lo; }
+
+// v_mad_u64_u32 with a wave-uniform second factor taken straight from an SGPR (no copy to a VGPR)
+__device__ __forceinline__ uint64_t mad_co_s(uint32_t a, uint32_t b, uint64_t c, lmask& co) {
+  uint64_t d;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(co) : "v"(a), "s"(b), "v"(c));
+  return d;
+}
+// y w 2^-64 mod q in (0, q + ceil(2 q^2 / 2^64)), y in [0, 2q), w < q; ntt64_mont_ok(q)
+// SW: w is wave-uniform and lives in SGPRs (the H round's scalar-loaded twiddles, N^-1, w1n)
+template <bool SW = false>
+__device__ __forceinline__ uint64_t mont_x(uint64_t y, uint64_t w, MontK& K) {
+  const uint32_t y0 = lo32(y), y1 = hi32(y), w0 = lo32(w), w1 = hi32(w);
+  const uint64_t p0 = (uint64_t)y0 * w0;
+  K.c1 = with_lo(K.c1, hi32(p0));
+  lmask b1, b2;
+  const uint64_t p1 = SW ? mad_co_s(y0, w1, K.c1, b1) : mad_co(y0, w1, K.c1, b1);  // asm: as C++ the two middle products are summed first and c1 added last
+  const uint64_t p2 = (uint64_t)y1 * w0 + p1;
+  K.cq = with_lo(K.cq, hi32(p2));
+  const uint64_t p3 = (uint64_t)y1 * w1 + K.cq;
+  const uint64_t Z = (uint64_t)lo32(p0) * K.q1;
+  const uint32_t m1 = sub_co(lo32(p2), lo32(Z), b1);
+  K.c0 = with_lo(K.c0, hi32(Z));
+  const uint64_t W = (uint64_t)m1 * K.q1 + K.c0;
+  const uint32_t r0 = subb_co(lo32(p3), lo32(W), b1, b2);
+  const uint32_t r1 = subb_co(hi32(p3), hi32(W), b2, b1);
+  return pair(r0, r1);
+}
+// (x, y) <- (x + w y, x - w y), lazy [0, 2q) in and out.  x + t < 3q + ceil(2 q^2 / 2^64) < 2^64
+// under the gate, so the sum needs no 65th bit and the borrow of s - 2q is the select mask.
+template <bool SW = false>
+__device__ __forceinline__ void fwd_bfly_m(uint64_t& x, uint64_t& y, uint64_t w, uint64_t q2, MontK& K) {
+  const uint64_t t = mont_x<SW>(y, w, K);
+  lmask b, b2, e, e2;
+  const uint64_t s = x + t;
+  const uint32_t u0 = sub_co(lo32(s), lo32(q2), b);
+  const uint32_t u1 = subb_co(hi32(s), hi32(q2), b, b2);
+  const uint32_t d0 = sub_co(lo32(x), lo32(t), e);
+  const uint32_t d1 = subb_co(hi32(x), hi32(t), e, e2);
+  const uint64_t d = pair(d0, d1);
+  const uint64_t f = d + q2;
+  x = pk(sel(b2, lo32(s), u0), sel(b2, hi32(s), u1));
+  y = pk(sel(e2, lo32(f), lo32(d)), sel(e2, hi32(f), hi32(d)));
+}
+// (x, y) <- (x + y, (x - y) w), lazy [0, 2q) in and out (x + y can reach 4q: the carry form)
+template <bool SW = false>
+__device__ __forceinline__ void inv_bfly_m(uint64_t& x, uint64_t& y, uint64_t w, uint64_t q2, MontK& K) {
+  lmask c, c2, b, b2, e, e2;
+  const uint32_t s0 = add_co(lo32(x), lo32(y), c);
+  const uint32_t s1 = addc_co(hi32(x), hi32(y), c, c2);
+  const uint32_t u0 = sub_co(s0, lo32(q2), b);
+  const uint32_t u1 = subb_co(s1, hi32(q2), b, b2);
+  const lmask m = c2 | ~b2;
+  const uint32_t d0 = sub_co(lo32(x), lo32(y), e);
+  const uint32_t d1 = subb_co(hi32(x), hi32(y), e, e2);
+  const uint64_t d = pair(d0, d1);
+  const uint64_t f = d + q2;
+  x = pk(sel(m, u0, s0), sel(m, u1, s1));
+  y = mont_x<SW>(pk(sel(e2, lo32(f), lo32(d)), sel(e2, hi32(f), hi32(d))), w, K);
+}
 // [0, 2q) -> [0, q)
 __device__ __forceinline__ uint64_t canon_x(uint64_t x, uint64_t q) {
   lmask b, b2;
@@ -214,11 +341,13 @@ struct Ntt64Args {
   // (ntt.go:153-203), then for N = 2^16 a lane-ordered copy of the ROW pass's last two stages:
   // row r, stage 14: [r*192 + 32 g + t] = tw[2^14 + 64 r + 2 t + g]       (g < 2,  t < 32)
   //        stage 15: [r*192 + 64 + 32 j + t] = tw[2^15 + 128 r + 4 t + j] (j < 4)
+  // MONT kernels: the same two tables as single words in Montgomery form (w 2^64 mod q, the
+  // reference's own representation), 8 B per entry, same indices
   const uint64_t* tw;
   uint64_t q, q2;
-  uint32_t nqhi, pad_;
-  uint64_t ninv, ninv_p;  // N^-1 and its Shoup quotient (inverse, last stage)
-  uint64_t w1n, w1n_p;    // twInv[1] N^-1
+  uint32_t nqhi, q1;      // -(q >> 32) mod 2^32 (Shoup), q >> 32 (MONT)
+  uint64_t ninv, ninv_p;  // N^-1 and its Shoup quotient (inverse, last stage); MONT: N^-1 in Montgomery form, ninv_p unused
+  uint64_t w1n, w1n_p;    // twInv[1] N^-1, likewise
   long long total_sub;    // batch * 2^(logN - 8)
   int logN, G0;
   int rev;  // 1: tiles in reverse order (a transform's second pass: Infinity Cache reuse, rg_bstore)
@@ -271,9 +400,35 @@ __device__ __forceinline__ void rg_bstore(uint64_t x, __amdgpu_buffer_rsrc_t r, 
 // LTW / MTW: the L round (PAT 2) and the M round (PAT 1) read their twiddles from the tile's LDS
 // copy `ltw` (248 entries staged by ntt16_tile: COL tw[8, 256); RP the row's lane-ordered L-round
 // copy, then its 56 stage 3-5 entries) instead of per-lane global loads
-template <int RK, int LO, int PAT, bool INV, bool SCALE, bool COL, bool RP, int PROBE>
+// MONT: the Montgomery product (mont_x) on single-word twiddles in Montgomery form, for moduli
+// that pass ntt64_mont_ok; every table entry, staged word and LDS slot is 8 B instead of a 16-B
+// (w, quotient) pair, and N^-1 / w1n stay in Montgomery form.  !MONT: Shoup's product (shoup_x).
+template <bool MONT>
+using tw_t = std::conditional_t<MONT, uint64_t, ulonglong2>;
+__device__ __forceinline__ void tw_put(uint64_t& w, uint64_t& wp, const ulonglong2& v) {
+  w = v.x;
+  wp = v.y;
+}
+__device__ __forceinline__ void tw_put(uint64_t& w, uint64_t& wp, uint64_t v) {
+  w = v;
+  wp = 0;
+}
+// table entry idx through the buffer resource
+template <bool MONT>
+__device__ __forceinline__ tw_t<MONT> tw_bload(__amdgpu_buffer_rsrc_t twr, uint32_t idx) {
+  if constexpr (MONT) {
+    const rg_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(twr, idx * 8u, 0, 0);
+    return pk(v.x, v.y);
+  } else {
+    const rg_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(twr, idx * 16u, 0, 0);
+    return ulonglong2{pk(v.x, v.y), pk(v.z, v.w)};
+  }
+}
+
+template <bool MONT, int RK, int LO, int PAT, bool INV, bool SCALE, bool COL, bool RP, int PROBE>
 __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_rsrc_t twr, uint64_t (&e)[8],
-                                            uint32_t hi, uint32_t t, const ulonglong2* ltw = nullptr) {
+                                            uint32_t hi, uint32_t t, [[maybe_unused]] MontK& K,
+                                            const tw_t<MONT>* ltw = nullptr) {  // K: MONT only (dead in the Shoup kernels)
   constexpr bool LTW = PAT == 2 && (COL || RP);
   constexpr int G0 = COL ? 0 : 8;
   // twiddle index independent of the lane: the H round of COL / RP tiles.  (The M round of COL
@@ -315,34 +470,23 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
       } else if constexpr (UNIFORM) {
         const uint32_t idx = (1u << (G0 + k)) + (hi << k) + (xof(rho0) >> (b + 1));
         const uint32_t iu = __builtin_amdgcn_readfirstlane(idx);
-        const ulonglong2 v = reinterpret_cast<const ulonglong2*>(a.tw)[iu];
-        w[j] = v.x;
-        wp[j] = v.y;
+        tw_put(w[j], wp[j], reinterpret_cast<const tw_t<MONT>*>(a.tw)[iu]);
       } else if constexpr (LTW && COL) {
-        const ulonglong2 v = ltw[(1u << k) + (xof(rho0) >> (b + 1)) - 8u];
-        w[j] = v.x;
-        wp[j] = v.y;
+        tw_put(w[j], wp[j], ltw[(1u << k) + (xof(rho0) >> (b + 1)) - 8u]);
       } else if constexpr (LTW) {
-        const ulonglong2 v = ltw[(k == 6 ? 32u * grp : 64u + 32u * (rho0 >> 1)) + t];
-        w[j] = v.x;
-        wp[j] = v.y;
+        tw_put(w[j], wp[j], ltw[(k == 6 ? 32u * grp : 64u + 32u * (rho0 >> 1)) + t]);
       } else if constexpr (MTW) {  // M round: COL tw[8, 64) ahead of the L round's; RP the row's stage 3-5 entries after them
-        const ulonglong2 v = COL ? ltw[(1u << k) + (xof(rho0) >> (b + 1)) - 8u]
-                                 : ltw[192u + (k == 3 ? 0u : k == 4 ? 8u : 24u) + (xof(rho0) >> (b + 1))];
-        w[j] = v.x;
-        wp[j] = v.y;
+        tw_put(w[j], wp[j],
+               COL ? ltw[(1u << k) + (xof(rho0) >> (b + 1)) - 8u]
+                   : ltw[192u + (k == 3 ? 0u : k == 4 ? 8u : 24u) + (xof(rho0) >> (b + 1))]);
       } else if constexpr (!COL && PAT == 2) {
         // ROW last round (stages 14, 15): lane-ordered copy after the natural table, lane t's
-        // j-th twiddle at t + 32 j, so every load is one coalesced 512-B run
+        // j-th twiddle at t + 32 j, so every load is one coalesced 512-B (MONT: 256-B) run
         const uint32_t pos = (65536u + hi * 192u) + (k == 6 ? 32u * grp : 64u + 32u * (rho0 >> 1)) + t;
-        const rg_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(twr, pos * 16u, 0, 0);
-        w[j] = pk(v.x, v.y);
-        wp[j] = pk(v.z, v.w);
+        tw_put(w[j], wp[j], tw_bload<MONT>(twr, pos));
       } else {
         const uint32_t idx = (1u << (G0 + k)) + (hi << k) + (xof(rho0) >> (b + 1));
-        const rg_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(twr, idx * 16u, 0, 0);
-        w[j] = pk(v.x, v.y);
-        wp[j] = pk(v.z, v.w);
+        tw_put(w[j], wp[j], tw_bload<MONT>(twr, idx));
       }
     }
 #pragma unroll
@@ -352,6 +496,20 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
       const int rho1 = rho0 + half;
       if constexpr ((PROBE & 2) != 0) {
         e[rho0] += e[rho1] ^ w[j] ^ wp[j];
+      } else if constexpr (MONT) {
+        // scalar twiddles (the H round's scalar loads; w1n and N^-1 are kernel arguments) feed
+        // the asm multiply from their SGPRs
+        constexpr bool SW = UNIFORM && (PROBE & 1) == 0;
+        if constexpr (!INV) {
+          fwd_bfly_m<SW>(e[rho0], e[rho1], w[j], a.q2, K);
+        } else {
+          if (last) {
+            inv_bfly_m<true>(e[rho0], e[rho1], w[j], a.q2, K);
+            e[rho0] = mont_x<true>(e[rho0], a.ninv, K);
+          } else {
+            inv_bfly_m<SW>(e[rho0], e[rho1], w[j], a.q2, K);
+          }
+        }
       } else if constexpr (!INV) {
         fwd_bfly_x(e[rho0], e[rho1], w[j], wp[j], a.q2, a.nqhi);
       } else {
@@ -371,8 +529,8 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
 //        L<->H pad (x>>5).
 // Every pattern pair was checked conflict-free for ds_*_b64 half-wave groups
 // (SQ_LDS_BANK_CONFLICT = 0 for COL in profiles/r01_ntt16_pmc_summary.txt).
-template <bool INV, bool COL, bool SCALE, bool CANON, bool RP, int PROBE = 0>
-__device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, uint64_t* lds, ulonglong2* ltw) {
+template <bool MONT, bool INV, bool COL, bool SCALE, bool CANON, bool RP, int PROBE = 0>
+__device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, uint64_t* lds, tw_t<MONT>* ltw) {
   const uint32_t tid = threadIdx.x;
   const uint32_t s = COL ? (tid & 15u) : (tid >> 5);
   const uint32_t t = COL ? (tid >> 4) : (tid & 31u);
@@ -389,14 +547,24 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
   const uint32_t hi = COL ? 0u : RP ? (uint32_t)__builtin_amdgcn_readfirstlane(tile & 255u) : (((tile << 4) + s) & 255u);
   uint64_t e[8];
   constexpr bool LTW = (COL || RP) && (PROBE & 1) == 0;
-  // The M and L rounds' 248 twiddle pairs, one 8-B word per thread (496 threads): the word is
-  // loaded after the tile's data loads and written to LDS just before the first barrier, so no
-  // wave waits for it before issuing its data loads (the first load's latency would otherwise
-  // open every tile).  COL: tw[8, 256); RP: the row's lane-ordered L-round copy, then its 56
-  // stage 3-5 entries.
-  const bool stv_on = LTW && tid < 496u;
+  // The M and L rounds' 248 twiddle pairs, one 8-B word per thread (496 threads; MONT: 248
+  // single words, 248 threads): the word is loaded after the tile's data loads and written to
+  // LDS just before the first barrier, so no wave waits for it before issuing its data loads
+  // (the first load's latency would otherwise open every tile).  COL: tw[8, 256); RP: the row's
+  // lane-ordered L-round copy, then its 56 stage 3-5 entries.
+  const bool stv_on = LTW && tid < (MONT ? 248u : 496u);
   uint32_t st_src = 0, st_dst = tid;
-  if constexpr (COL) {
+  if constexpr (MONT) {
+    if constexpr (COL) {
+      st_src = 8u + tid;
+    } else if (tid < 192u) {
+      st_src = 65536u + hi * 192u + tid;
+    } else {
+      const uint32_t ent = tid - 192u;
+      const uint32_t kk = ent < 8u ? 3u : ent < 24u ? 4u : 5u, j = ent - (kk == 3u ? 0u : kk == 4u ? 8u : 24u);
+      st_src = (1u << (8u + kk)) + (hi << kk) + j;
+    }
+  } else if constexpr (COL) {
     st_src = 16u + tid;
   } else if (tid < 384u) {
     st_src = 2u * (65536u + hi * 192u) + tid;
@@ -442,8 +610,10 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
   auto offM = [](int y) { return 64 * y + 16 * (y >> 1); };
   const uint32_t rH = 288 * s + t, rM = 288 * s + 36 * (t >> 2) + (t & 3), rL9 = 288 * s + 9 * t,
                  rL8 = 288 * s + 8 * t + (t >> 2);
+  MontK K{};  // the Shoup kernels carry it unused
+  if constexpr (MONT) K = mont_k(a.q1);
   if constexpr (!INV) {
-    ntt16_round<3, 5, 0, false, false, COL, RP, PROBE>(a, twr, e, hi, t);
+    ntt16_round<MONT, 3, 5, 0, false, false, COL, RP, PROBE>(a, twr, e, hi, t, K);
     stage_write();
     // exchange H -> M
 #pragma unroll
@@ -451,7 +621,7 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
     __syncthreads();
 #pragma unroll
     for (int y = 0; y < 8; ++y) e[y] = lds[COL ? bM + offM(y) : rM + 4 * y];
-    ntt16_round<3, 2, 1, false, false, COL, RP, PROBE>(a, twr, e, hi, t, ltw);
+    ntt16_round<MONT, 3, 2, 1, false, false, COL, RP, PROBE>(a, twr, e, hi, t, K, ltw);
     __syncthreads();
     // exchange M -> L
 #pragma unroll
@@ -459,7 +629,7 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 8; ++r) e[r] = lds[COL ? bL + 16 * r : rL9 + r];
-    ntt16_round<2, 0, 2, false, false, COL, RP, PROBE>(a, twr, e, hi, t, ltw);
+    ntt16_round<MONT, 2, 0, 2, false, false, COL, RP, PROBE>(a, twr, e, hi, t, K, ltw);
     if (CANON) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) e[r] = canon_x(e[r], a.q);
@@ -488,14 +658,14 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
       __syncthreads();
     }
     if constexpr (COL && LTW) __syncthreads();  // the staged twiddles (ROW's transpose has its barrier)
-    ntt16_round<2, 0, 2, true, SCALE, COL, RP, PROBE>(a, twr, e, hi, t, ltw);
+    ntt16_round<MONT, 2, 0, 2, true, SCALE, COL, RP, PROBE>(a, twr, e, hi, t, K, ltw);
     // exchange L -> M
 #pragma unroll
     for (int r = 0; r < 8; ++r) lds[COL ? bL + 16 * r : rL9 + r] = e[r];
     __syncthreads();
 #pragma unroll
     for (int y = 0; y < 8; ++y) e[y] = lds[COL ? bM + offM(y) : rM + 4 * y + (y >> 1)];
-    ntt16_round<3, 2, 1, true, SCALE, COL, RP, PROBE>(a, twr, e, hi, t, ltw);
+    ntt16_round<MONT, 3, 2, 1, true, SCALE, COL, RP, PROBE>(a, twr, e, hi, t, K, ltw);
     __syncthreads();
     // exchange M -> H
 #pragma unroll
@@ -503,7 +673,7 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
     __syncthreads();
 #pragma unroll
     for (int y = 0; y < 8; ++y) e[y] = lds[COL ? bH + 576 * y : rH + 36 * y];
-    ntt16_round<3, 5, 0, true, SCALE, COL, RP, PROBE>(a, twr, e, hi, t);
+    ntt16_round<MONT, 3, 5, 0, true, SCALE, COL, RP, PROBE>(a, twr, e, hi, t, K);
     if (CANON) {
 #pragma unroll
       for (int y = 0; y < 8; ++y) e[y] = canon_x(e[y], a.q);
@@ -520,12 +690,12 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
   }
 }
 
-template <bool INV, bool COL, bool SCALE, bool CANON, bool RP = false, int MINW = 1, int PROBE = 0>
+template <bool MONT, bool INV, bool COL, bool SCALE, bool CANON, bool RP = false, int MINW = 1, int PROBE = 0>
 __global__ __launch_bounds__(512, MINW) void ntt16_pass(Ntt64Args a) {
   __shared__ uint64_t lds[16 * 288];
-  __shared__ ulonglong2 ltw[COL || RP ? 248 : 1];  // 39.9 KiB per workgroup with lds: 4 per CU
+  __shared__ tw_t<MONT> ltw[COL || RP ? 248 : 1];  // 39.9 KiB (MONT: 37.9 KiB) per workgroup with lds: 4 per CU
   const uint32_t tile = a.rev ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
-  ntt16_tile<INV, COL, SCALE, CANON, RP, PROBE>(a, tile, lds, ltw);
+  ntt16_tile<MONT, INV, COL, SCALE, CANON, RP, PROBE>(a, tile, lds, ltw);
 }
 
 #endif  // __HIPCC__

@@ -2,7 +2,9 @@
 // they cover: N = 2^16 as two 8-stage passes, q < 2^63 with q mod 2^32 == 1 (the config-2
 // jindo-modulus prime 47104^4 + 1 and every other p - 1 = b^(2^e) with b even).  Other shapes
 // keep the generic kernels of ntt_kernels.hpp.  RINGO_NTT_KERNEL=r* forces the generic path
-// (experiments build only, common.hpp).
+// (experiments build only, common.hpp).  Moduli that pass ntt64_mont_ok (q / 2^64 <= 0.2808: the
+// config-2 prime) take the MONT instantiations, the Montgomery twiddle product on single-word
+// tables; the others (up to q < 2^63) keep Shoup's product.
 #include "ntt64.hpp"
 #include "ntt_plan.hpp"
 
@@ -19,21 +21,26 @@ static bool lazy_disabled() {
 
 // ROW passes tile the same row of 16 polynomials when the chunk allows it (RP, twiddles
 // shared by the whole tile); otherwise 16 consecutive rows of one polynomial
-template <bool INV, bool COL, bool SCALE, bool CANON>
-static rg_status launch64(const Ntt64Args& a, size_t polys, hipStream_t st) {
+template <bool MONT, bool INV, bool COL, bool SCALE, bool CANON>
+static rg_status launch64m(const Ntt64Args& a, size_t polys, hipStream_t st) {
   const long long tiles = a.total_sub / 16;
   if (measure_probe() == 4) {  // bench.py's compute floor (rg_set_probe, experiments build): no HBM data movement
     if (!COL && polys % 16 == 0)
-      hipLaunchKernelGGL((ntt16_pass<INV, COL, SCALE, CANON, true, 1, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
+      hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, true, 1, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
     else
-      hipLaunchKernelGGL((ntt16_pass<INV, COL, SCALE, CANON, false, 1, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
+      hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, false, 1, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
     return check_launch("ntt16_pass (probe)");
   }
   if (!COL && polys % 16 == 0)
-    hipLaunchKernelGGL((ntt16_pass<INV, COL, SCALE, CANON, true>), dim3((unsigned)tiles), dim3(512), 0, st, a);
+    hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, true>), dim3((unsigned)tiles), dim3(512), 0, st, a);
   else
-    hipLaunchKernelGGL((ntt16_pass<INV, COL, SCALE, CANON, false>), dim3((unsigned)tiles), dim3(512), 0, st, a);
+    hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, false>), dim3((unsigned)tiles), dim3(512), 0, st, a);
   return check_launch("ntt16_pass");
+}
+
+template <bool INV, bool COL, bool SCALE, bool CANON>
+static rg_status launch64(const Ntt64Args& a, bool mont, size_t polys, hipStream_t st) {
+  return mont ? launch64m<true, INV, COL, SCALE, CANON>(a, polys, st) : launch64m<false, INV, COL, SCALE, CANON>(a, polys, st);
 }
 
 rg_status ntt64_run(const NttLaunch& p, hipStream_t st, bool* handled) {
@@ -44,13 +51,15 @@ rg_status ntt64_run(const NttLaunch& p, hipStream_t st, bool* handled) {
   *handled = true;
   const size_t N = (size_t)1 << p.logN;
   Ntt64Args a{};
-  a.tw = p.tw;
+  const bool mont = p.tw_mont != nullptr && ntt64_mont_ok(q);
+  a.tw = mont ? p.tw_mont : p.tw;
   a.q = q;
   a.q2 = 2 * q;
   a.nqhi = 0u - (uint32_t)(q >> 32);
-  a.ninv = p.nsc[0];
+  a.q1 = (uint32_t)(q >> 32);
+  a.ninv = mont ? p.nsc_mont : p.nsc[0];
   a.ninv_p = p.nsc_sh;
-  a.w1n = p.w1n[0];
+  a.w1n = mont ? p.w1n_mont : p.w1n[0];
   a.w1n_p = p.w1n_sh;
   a.logN = p.logN;
   static size_t chunk_polys = 0;
@@ -66,21 +75,21 @@ rg_status ntt64_run(const NttLaunch& p, hipStream_t st, bool* handled) {
       a.out = p.out + b0 * N;
       a.G0 = 0;
       a.rev = 0;
-      RG_TRY((launch64<false, true, false, false>(a, nb, st)));
+      RG_TRY((launch64<false, true, false, false>(a, mont, nb, st)));
       a.in = a.out;
       a.G0 = 8;
       a.rev = 1;  // reverse tile order: reads what the first pass wrote last first (ntt64.hpp)
-      RG_TRY((launch64<false, false, false, true>(a, nb, st)));
+      RG_TRY((launch64<false, false, false, true>(a, mont, nb, st)));
     } else {
       a.in = p.in + b0 * N;
       a.out = p.out + b0 * N;
       a.G0 = 8;
       a.rev = 0;
-      RG_TRY((launch64<true, false, false, false>(a, nb, st)));
+      RG_TRY((launch64<true, false, false, false>(a, mont, nb, st)));
       a.in = a.out;
       a.G0 = 0;
       a.rev = 1;  // reverse tile order: reads what the first pass wrote last first (ntt64.hpp)
-      RG_TRY((launch64<true, true, true, true>(a, nb, st)));
+      RG_TRY((launch64<true, true, true, true>(a, mont, nb, st)));
     }
   }
   return RG_OK;

@@ -21,6 +21,10 @@ struct NttLaunch {
   uint64_t nsc_sh;
   const uint64_t* w1n;
   uint64_t w1n_sh;
+  // L = 1, N = 2^16, ntt64_mont_ok(q) (ntt64.hpp): the direction's table as single words in
+  // Montgomery form with its lane-ordered ROW copy, N^-1 and twInv[1] N^-1 likewise; else null
+  const uint64_t* tw_mont = nullptr;
+  uint64_t nsc_mont = 0, w1n_mont = 0;
   int logN;
   bool shoup, inv, tiled;
   bool halving;  // rank_inv == N^-1: the wide pass's per-stage halving scales the inverse correctly

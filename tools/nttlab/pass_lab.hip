@@ -62,7 +62,7 @@ static uint64_t powmod(uint64_t a, uint64_t e, uint64_t q) {
 template <bool INV, bool COL, bool SCALE, bool CANON, int MINW, int PROBE>
 static void launch(const Ntt64Args& a, int grid) {
   (void)grid;
-  hipLaunchKernelGGL((ntt16_pass<INV, COL, SCALE, CANON, (PROBE & 512) != 0, MINW, (PROBE & 255)>), dim3((unsigned)(a.total_sub / 16)), dim3(512), 0, 0, a);
+  hipLaunchKernelGGL((ntt16_pass<false, INV, COL, SCALE, CANON, (PROBE & 512) != 0, MINW, (PROBE & 255)>), dim3((unsigned)(a.total_sub / 16)), dim3(512), 0, 0, a);
 }
 
 template <int MINW, int PROBE = 0>
