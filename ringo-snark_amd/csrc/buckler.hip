@@ -112,21 +112,13 @@ __global__ __launch_bounds__(256) void circuit_kernel(CircArgs<L> a) {
   cpy<L>(a.out + j * L, acc);
 }
 
-template <int L>
-static FieldParams<L> params_of(const rg_field* f) {
-  FieldParams<L> F;
-  memcpy(F.q, f->q, 8 * L);
-  F.qinv = f->qinv;
-  return F;
-}
-
 static unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 
 template <int L>
 static rg_status embed_L(const rg_field* f, uint64_t* out, const uint64_t* src, long long rank, long long emb,
                          long long batch, const uint64_t* rnd, hipStream_t st) {
-  hipLaunchKernelGGL(embed_kernel<L>, dim3(blocks_of(batch * emb)), dim3(256), 0, st, params_of<L>(f), out, src, rank,
-                     emb, batch, rnd);
+  hipLaunchKernelGGL(embed_kernel<L>, dim3(blocks_of(batch * emb)), dim3(256), 0, st, field_params<L>(f), out, src,
+                     rank, emb, batch, rnd);
   return check_launch("buckler encode");
 }
 
@@ -134,7 +126,7 @@ template <int L>
 static rg_status circuit_L(const rg_circuit* c, long long rank, const uint64_t* bc, const uint64_t* w,
                            const uint64_t* pw, uint64_t* out, hipStream_t st) {
   CircArgs<L> a;
-  a.F = params_of<L>(&c->f);
+  a.F = field_params<L>(&c->f);
   const char* base = c->prog.as<char>();
   a.term_off = reinterpret_cast<const uint32_t*>(base);
   a.pw_idx = reinterpret_cast<const int*>(base + c->off_pw);
@@ -150,16 +142,6 @@ static rg_status circuit_L(const rg_circuit* c, long long rank, const uint64_t* 
   hipLaunchKernelGGL(circuit_kernel<L>, dim3(blocks_of(rank)), dim3(256), 0, st, a);
   return check_launch("buckler evalCircuit");
 }
-
-#define RG_DISPATCH_L(L_, CALL)         \
-  switch (L_) {                         \
-    case 1: return CALL(1);             \
-    case 2: return CALL(2);             \
-    case 4: return CALL(4);             \
-    case 7: return CALL(7);             \
-    case 14: return CALL(14);           \
-    default: return RG_ERR_UNSUPPORTED; \
-  }
 
 static bool lt_q(const uint64_t* x, const rg_field* f) {
   for (int i = f->L - 1; i >= 0; --i)
@@ -193,9 +175,8 @@ rg_status rg_buckler_encode_dev(const rg_ntt* t, size_t embed_rank, uint64_t* d_
     RG_TRY(rg_ntt_inv_dev(t, d_scratch, d_v, batch, stream));
     src = d_scratch;
   }
-#define RG_EMB(L) embed_L<L>(f, d_out, src, rank, emb, (long long)batch, d_rand, st)
-  RG_DISPATCH_L(f->L, RG_EMB)
-#undef RG_EMB
+  return dispatch_limbs(f->L,
+                        [&](auto Lc) { return embed_L<Lc()>(f, d_out, src, rank, emb, (long long)batch, d_rand, st); });
 }
 
 rg_status rg_buckler_encode(const rg_ntt* t, size_t embed_rank, uint64_t* out, const uint64_t* v,
@@ -287,9 +268,9 @@ rg_status rg_buckler_eval_circuit_dev(const rg_circuit* c, size_t rank, const ui
   if ((c->max_w >= 0 && !d_w) || (c->max_pw >= 0 && !d_pw)) return RG_ERR_INVALID;
   if (rank == 0) return RG_OK;
   hipStream_t st = as_stream(stream);
-#define RG_CIRC(L) circuit_L<L>(c, (long long)rank, d_batch_const, d_w, d_pw, d_out, st)
-  RG_DISPATCH_L(c->f.L, RG_CIRC)
-#undef RG_CIRC
+  return dispatch_limbs(c->f.L, [&](auto Lc) {
+    return circuit_L<Lc()>(c, (long long)rank, d_batch_const, d_w, d_pw, d_out, st);
+  });
 }
 
 rg_status rg_buckler_eval_circuit(const rg_circuit* c, size_t rank, const uint64_t* batch_const, const uint64_t* w,

@@ -199,8 +199,7 @@ __global__ __launch_bounds__(256) void dcmp_two_final_kernel(DcmpConst<L> K, uin
 template <int L>
 static DcmpConst<L> consts(const rg_dcmp* h) {
   DcmpConst<L> K;
-  memcpy(K.F.q, h->f.q, 8 * L);
-  K.F.qinv = h->f.qinv;
+  K.F = field_params<L>(&h->f);
   memcpy(K.one, h->one, 8 * L);
   memcpy(K.neg_one, h->neg_one, 8 * L);
   return K;
@@ -250,32 +249,16 @@ static rg_status two_L(const rg_dcmp* h, const uint64_t* w, long long batch, lon
   return check_launch("dcmp two-norm digits");
 }
 
-#define RG_DCMP_DISPATCH(L_, CALL)      \
-  switch (L_) {                         \
-    case 1: return CALL(1);             \
-    case 2: return CALL(2);             \
-    case 4: return CALL(4);             \
-    case 7: return CALL(7);             \
-    case 14: return CALL(14);           \
-    default: return RG_ERR_UNSUPPORTED; \
-  }
-
 static rg_status launch_inf(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
                             hipStream_t st) {
-#define RG_CALL(L) inf_L<L>(h, w, batch, rank, out, st)
-  RG_DCMP_DISPATCH(h->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(h->f.L, [&](auto Lc) { return inf_L<Lc()>(h, w, batch, rank, out, st); });
 }
 static rg_status launch_proj(const rg_dcmp* h, const uint64_t* w, long long rank, uint64_t* out, hipStream_t st) {
-#define RG_CALL(L) proj_L<L>(h, w, rank, out, st)
-  RG_DCMP_DISPATCH(h->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(h->f.L, [&](auto Lc) { return proj_L<Lc()>(h, w, rank, out, st); });
 }
 static rg_status launch_two(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
                             uint64_t* sq, uint64_t* scratch, hipStream_t st) {
-#define RG_CALL(L) two_L<L>(h, w, batch, rank, out, sq, scratch, st)
-  RG_DCMP_DISPATCH(h->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(h->f.L, [&](auto Lc) { return two_L<Lc()>(h, w, batch, rank, out, sq, scratch, st); });
 }
 
 static bool inf_args_ok(const rg_dcmp* h, const void* w, size_t batch, size_t rank, const void* out) {

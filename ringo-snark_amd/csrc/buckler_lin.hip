@@ -325,13 +325,6 @@ __global__ __launch_bounds__(256) void lin_kernel(LinArgs<L> a) {
 
 // ---- host side ----------------------------------------------------------------------------------
 template <int L>
-static FieldParams<L> fp(const rg_field* f) {
-  FieldParams<L> F;
-  memcpy(F.q, f->q, 8 * L);
-  F.qinv = f->qinv;
-  return F;
-}
-template <int L>
 static El<L> el(const uint64_t* x) {
   El<L> e;
   memcpy(e.v, x, 8 * L);
@@ -345,19 +338,9 @@ static bool same_field(const rg_field* a, const rg_field* b) {
   return a->L == b->L && memcmp(a->q, b->q, 8 * a->L) == 0;
 }
 
-#define RG_DISPATCH_L(L_, CALL)         \
-  switch (L_) {                         \
-    case 1: return CALL(1);             \
-    case 2: return CALL(2);             \
-    case 4: return CALL(4);             \
-    case 7: return CALL(7);             \
-    case 14: return CALL(14);           \
-    default: return RG_ERR_UNSUPPORTED; \
-  }
-
 template <int L>
 static rg_status revscale_L(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
-  hipLaunchKernelGGL(revscale_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, fp<L>(&c->f),
+  hipLaunchKernelGGL(revscale_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, field_params<L>(&c->f),
                      el<L>(c->scale), out, v, c->rank, batch);
   return check_launch("ntt checker transpose");
 }
@@ -368,18 +351,18 @@ template <int L>
 static rg_status proj_fwd_L(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch,
                             uint64_t* scratch, hipStream_t st) {
   const long long chunks = proj_chunks(c->rank);
-  hipLaunchKernelGGL(proj_fwd_kernel<L>, dim3((unsigned)chunks, (unsigned)batch), dim3(kProjRows), 0, st, fp<L>(&c->f),
-                     scratch, v, c->bits.as<uint32_t>(), c->rank);
+  hipLaunchKernelGGL(proj_fwd_kernel<L>, dim3((unsigned)chunks, (unsigned)batch), dim3(kProjRows), 0, st,
+                     field_params<L>(&c->f), scratch, v, c->bits.as<uint32_t>(), c->rank);
   RG_TRY(check_launch("proj transform"));
-  hipLaunchKernelGGL(proj_sum_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, fp<L>(&c->f), out, scratch,
-                     c->rank, chunks, batch);
+  hipLaunchKernelGGL(proj_sum_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, field_params<L>(&c->f), out,
+                     scratch, c->rank, chunks, batch);
   return check_launch("proj transform sum");
 }
 
 template <int L>
 static rg_status proj_tr_L(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
   hipLaunchKernelGGL(proj_tr_kernel<L>, dim3((unsigned)proj_chunks(c->rank), (unsigned)batch), dim3(kProjRows), 0, st,
-                     fp<L>(&c->f), out, v, c->bits.as<uint32_t>(), c->rank);
+                     field_params<L>(&c->f), out, v, c->bits.as<uint32_t>(), c->rank);
   return check_launch("proj transpose");
 }
 
@@ -387,26 +370,27 @@ template <int L>
 static rg_status recompose_L(const rg_linchecker* c, bool tr, uint64_t* out, const uint64_t* v, long long batch,
                              hipStream_t st) {
   if (tr)
-    hipLaunchKernelGGL(recompose_tr_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, fp<L>(&c->f), out, v,
-                       c->base.as<uint64_t>(), c->nb, c->rank, batch);
+    hipLaunchKernelGGL(recompose_tr_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, field_params<L>(&c->f),
+                       out, v, c->base.as<uint64_t>(), c->nb, c->rank, batch);
   else
-    hipLaunchKernelGGL(recompose_fwd_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, fp<L>(&c->f), out, v,
-                       c->base.as<uint64_t>(), c->nb, c->rank, batch);
+    hipLaunchKernelGGL(recompose_fwd_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st,
+                       field_params<L>(&c->f), out, v, c->base.as<uint64_t>(), c->nb, c->rank, batch);
   return check_launch("recompose checker");
 }
 
 template <int L>
 static rg_status powers_L(const rg_field* f, const uint64_t* c, long long n, uint64_t* out, hipStream_t st) {
   const long long lanes = (n + kPowBlock - 1) / kPowBlock;
-  hipLaunchKernelGGL(powers_kernel<L>, dim3(grid256(lanes)), dim3(256), 0, st, fp<L>(f), el<L>(f->one), c, out, n);
+  hipLaunchKernelGGL(powers_kernel<L>, dim3(grid256(lanes)), dim3(256), 0, st, field_params<L>(f), el<L>(f->one), c,
+                     out, n);
   return check_launch("powers");
 }
 
 template <int L>
 static rg_status mask_L(const rg_field* f, long long rank, long long mask_rank, long long emb, const uint64_t* r,
                         uint64_t* mask, uint64_t* mask_sum, hipStream_t st) {
-  hipLaunchKernelGGL(mask_kernel<L>, dim3(grid256(emb)), dim3(256), 0, st, fp<L>(f), mask, mask_sum, r, rank, mask_rank,
-                     emb);
+  hipLaunchKernelGGL(mask_kernel<L>, dim3(grid256(emb)), dim3(256), 0, st, field_params<L>(f), mask, mask_sum, r, rank,
+                     mask_rank, emb);
   return check_launch("sumcheck mask");
 }
 
@@ -425,7 +409,7 @@ template <int L>
 static rg_status lin_L(const rg_lincheck* lc, const uint64_t* ecd, const uint64_t* w, const uint64_t* bc, uint64_t* out,
                        long long emb, hipStream_t st) {
   LinArgs<L> a;
-  a.F = fp<L>(ntt_field(lc->emb));
+  a.F = field_params<L>(ntt_field(lc->emb));
   a.pair_off = lc->prog.as<uint32_t>();
   a.pairs = a.pair_off + lc->chk.size() + 1;
   a.ecd = ecd;
@@ -454,32 +438,22 @@ static long long mod_inverse(long long x, long long m) {
 
 // the limb-count dispatch of each launcher
 static rg_status revscale(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
-#define RG_CALL(L) revscale_L<L>(c, out, v, batch, st)
-  RG_DISPATCH_L(c->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(c->f.L, [&](auto Lc) { return revscale_L<Lc()>(c, out, v, batch, st); });
 }
 static rg_status proj_fwd(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, uint64_t* scratch,
                           hipStream_t st) {
-#define RG_CALL(L) proj_fwd_L<L>(c, out, v, batch, scratch, st)
-  RG_DISPATCH_L(c->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(c->f.L, [&](auto Lc) { return proj_fwd_L<Lc()>(c, out, v, batch, scratch, st); });
 }
 static rg_status proj_tr(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
-#define RG_CALL(L) proj_tr_L<L>(c, out, v, batch, st)
-  RG_DISPATCH_L(c->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(c->f.L, [&](auto Lc) { return proj_tr_L<Lc()>(c, out, v, batch, st); });
 }
 static rg_status recompose(const rg_linchecker* c, bool tr, uint64_t* out, const uint64_t* v, long long batch,
                            hipStream_t st) {
-#define RG_CALL(L) recompose_L<L>(c, tr, out, v, batch, st)
-  RG_DISPATCH_L(c->f.L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(c->f.L, [&](auto Lc) { return recompose_L<Lc()>(c, tr, out, v, batch, st); });
 }
 static rg_status lin_pass(const rg_lincheck* lc, const uint64_t* ecd, const uint64_t* w, const uint64_t* bc,
                           uint64_t* out, long long emb, hipStream_t st) {
-#define RG_CALL(L) lin_L<L>(lc, ecd, w, bc, out, emb, st)
-  RG_DISPATCH_L(ntt_field(lc->emb)->L, RG_CALL)
-#undef RG_CALL
+  return dispatch_limbs(ntt_field(lc->emb)->L, [&](auto Lc) { return lin_L<Lc()>(lc, ecd, w, bc, out, emb, st); });
 }
 
 static rg_status checker_apply(const rg_linchecker* c, bool tr, uint64_t* d_out, const uint64_t* d_v, size_t batch,
@@ -640,9 +614,7 @@ rg_status rg_buckler_powers_dev(const rg_field* f, const uint64_t* d_c, size_t n
   if (!f || !d_c || (n && !d_out) || d_out == d_c || n > ((size_t)1 << 40)) return RG_ERR_INVALID;
   if (n == 0) return RG_OK;
   hipStream_t st = as_stream(stream);
-#define RG_PW(L) powers_L<L>(f, d_c, (long long)n, d_out, st)
-  RG_DISPATCH_L(f->L, RG_PW)
-#undef RG_PW
+  return dispatch_limbs(f->L, [&](auto Lc) { return powers_L<Lc()>(f, d_c, (long long)n, d_out, st); });
 }
 
 rg_status rg_buckler_powers(const rg_field* f, const uint64_t* c, size_t n, uint64_t* out) {
@@ -663,9 +635,9 @@ rg_status rg_buckler_sumcheck_mask_dev(const rg_field* f, size_t rank, size_t ma
   if (rank == 0 || mask_rank < rank || mask_rank > emb_rank || emb_rank > ((size_t)1 << 40)) return RG_ERR_INVALID;
   if (d_rand == d_mask || d_mask_sum == d_mask || d_mask_sum == d_rand) return RG_ERR_INVALID;
   hipStream_t st = as_stream(stream);
-#define RG_MK(L) mask_L<L>(f, (long long)rank, (long long)mask_rank, (long long)emb_rank, d_rand, d_mask, d_mask_sum, st)
-  RG_DISPATCH_L(f->L, RG_MK)
-#undef RG_MK
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    return mask_L<Lc()>(f, (long long)rank, (long long)mask_rank, (long long)emb_rank, d_rand, d_mask, d_mask_sum, st);
+  });
 }
 
 rg_status rg_buckler_sumcheck_mask(const rg_field* f, size_t rank, size_t mask_rank, size_t emb_rank,
@@ -708,10 +680,10 @@ rg_status rg_buckler_check_finish_dev(const rg_ntt* emb_plan, size_t rank, uint6
   // QuoRemByVanishing(eval, rank): quoPoly into scratch, remPoly over eval
   RG_TRY(rg_poly_quorem_vanishing_dev(f, emb, (long long)rank, d_scratch, d_eval, d_eval, 1, stream));
   hipStream_t st = as_stream(stream);
-#define RG_TL(L) \
-  tail_L<L>(d_quo, d_rem_lo, d_rem_hi, d_scratch, d_eval, (long long)n_quo, (long long)rank, (long long)jindo_rank, st)
-  RG_DISPATCH_L(f->L, RG_TL)
-#undef RG_TL
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    return tail_L<Lc()>(d_quo, d_rem_lo, d_rem_hi, d_scratch, d_eval, (long long)n_quo, (long long)rank,
+                        (long long)jindo_rank, st);
+  });
 }
 
 rg_status rg_buckler_check_finish(const rg_ntt* emb_plan, size_t rank, const uint64_t* eval, const uint64_t* scale,

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ringo.h"
+#include "field.hpp"
 
 namespace rg {
 
@@ -139,3 +141,31 @@ struct rg_field {
   uint64_t one[16];
   bool spare_bit;  // q < 2^(64L-1)
 };
+
+namespace rg {
+
+// the kernel-argument form of a field handle
+template <int L>
+inline FieldParams<L> field_params(const rg_field* f) {
+  FieldParams<L> F;
+  memcpy(F.q, f->q, 8 * L);
+  F.qinv = f->qinv;
+  return F;
+}
+
+// The one switch on a field's limb count: f(std::integral_constant<int, L>) for the five counts
+// the kernels are instantiated for, e.g.
+//   dispatch_limbs(f->L, [&](auto Lc) { return vec_L<Lc()>(f, ...); });
+template <class F>
+inline rg_status dispatch_limbs(int L, F&& f) {
+  switch (L) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 14: return f(std::integral_constant<int, 14>{});
+    default: return RG_ERR_UNSUPPORTED;
+  }
+}
+
+}  // namespace rg

@@ -23,8 +23,9 @@
 //                      primes), floor shift by the cut, Euclidean mod q', MForm, NTT in the
 //                      destination ring (prover.go:164-176, rns.go:76-114).
 //   5. the MAC + round_kernel again for the outer commitment (prover.go:180-202).
-// Evaluate: every MulCoeffsMontgomeryThenAdd loop is a J = 1 dot product on mac_kernel
-// (rg_jindo_eval_*), plus rns_reduce_kernel after a cross-GPU sum of partial openBatches.
+// Evaluate and Verifier.Verify: every MulCoeffsMontgomeryThenAdd loop is a J = 1 dot product on
+// mac_kernel; their entry points and the verifier's norm, decode and dot kernels are
+// jindo_verify.hip (shared definitions: jindo_impl.hpp).
 // All residues are canonical, so results are bit-exact against the reference's Lattigo
 // calls given the same primes (Lattigo conventions restated: see DESIGN.md, "parity").
 #include <algorithm>
@@ -36,58 +37,16 @@
 #include <vector>
 
 #include "ck_crs.hpp"
-#include "common.hpp"
 #include "csprng.hpp"
 #include "digits_dc.hpp"
 #include "csprng_host.hpp"
-#include "field.hpp"
 #include "host_field.hpp"
+#include "jindo_impl.hpp"
 #include "mac_mfma.hpp"
 #include "ntt64.hpp"
 
 namespace rg {
 
-constexpr int kMaxQ = 4;     // RNS limbs per ring
-constexpr int kMaxD = 1024;  // ring degree supported by the LDS kernels
-constexpr int kMaxJ = 32;    // MSIS rank accumulated per thread
-
-struct RnsPrime {
-  uint64_t q;
-  uint64_t rinv, rinv_sh;    // 2^-64 mod q (IMForm)
-  uint64_t r64, r64_sh;      // 2^64 mod q (MForm)
-  uint64_t one_sh;           // floor(2^64 / q): x mod q = shoup(x, 1)
-  uint64_t ninv, ninv_sh;    // d^-1 mod q
-  uint64_t bmod, bmod_sh;    // base mod q
-  uint64_t rw1, rw1_sh;      // 2^64 w1 mod q, w1 = the forward table's first-stage root (prep256 stage 0)
-};
-
-struct RingDev {
-  int n;                    // limbs
-  RnsPrime p[kMaxQ];
-  const ulonglong2* fwd;    // [n][d] (w, w') psi^brv
-  const ulonglong2* bwd;    // [n][d] psi^-brv
-};
-
-// CRT (Garner) constants for a source ring
-struct CrtDev {
-  int n;
-  uint64_t q[kMaxQ];
-  uint64_t inv[kMaxQ][kMaxQ], inv_sh[kMaxQ][kMaxQ];  // inv[j][k] = q_k^-1 mod q_j (k < j)
-  uint64_t Q[4], Qhalf[4];                            // product (4 words) and floor(Q/2)
-};
-
-// destination mod constants: 2^(64k) mod q' for multiword reduction
-struct DstDev {
-  int n;
-  uint64_t pw[kMaxQ][4], pw_sh[kMaxQ][4];
-};
-
-// ------------------------------------------------------------------------------------------
-// device helpers
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t sh_mul(uint64_t y, uint64_t w, uint64_t wp, uint64_t q) {
-  return shoup_mul(y, w, wp, q);
-}
 __device__ __forceinline__ uint64_t signed_residue(long long c, uint64_t q) {
   // setCoeffSigned (utils.go:49-61): c >= 0 -> c ; else Go's c%q + q (== q when q | c; the
   // following MForm maps that to 0 either way)
@@ -114,26 +73,6 @@ __device__ void ntt_lds(uint64_t* p, int d, const ulonglong2* roots, uint64_t q,
     __syncthreads();
   }
 }
-// inverse (GS, bit-reversed -> natural), times d^-1
-__device__ void intt_lds(uint64_t* p, int d, const ulonglong2* roots, const RnsPrime& P, int ti, int nt, bool active) {
-  const uint64_t q = P.q;
-  for (int m = d >> 1, t = 1, lt = 0; m >= 1; m >>= 1, t <<= 1, ++lt) {
-    if (active) {
-      for (int k = ti; k < (d >> 1); k += nt) {
-        const int i = k >> lt, j = (i << (lt + 1)) + (k & (t - 1));
-        const ulonglong2 w = roots[m + i];
-        const uint64_t u = p[j], v = p[j + t];
-        p[j] = mod_add(u, v, q);
-        p[j + t] = sh_mul(mod_sub(u, v, q), w.x, w.y, q);
-      }
-    }
-    __syncthreads();
-  }
-  if (active)
-    for (int k = ti; k < d; k += nt) p[k] = sh_mul(p[k], P.ninv, P.ninv_sh, q);
-  __syncthreads();
-}
-
 // ------------------------------------------------------------------------------------------
 // 1. digits
 // ------------------------------------------------------------------------------------------
@@ -443,9 +382,15 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
   asm volatile("" ::: "memory");
 }
-template <int RK, int LO, int PAT, int SP0 = 0, bool LAZY = false>
-__device__ __forceinline__ void prep_round(uint64_t (&e)[8], const ulonglong2* roots, uint64_t q, uint64_t q2,
-                                           uint32_t t) {
+
+// The index algebra of the wave transforms (prep256_kernel, round256_kernel), in one place.
+// A lane (t = lane & 31) holds 8 points e[0..8) of its half-wave's 256-point limb in one of three
+// patterns PAT: H (point t + 32 rho), M (rho in bits 2-4) and L (point 8 t + rho).  A round of RK
+// radix-2 stages on bits LO .. LO + RK - 1 runs in registers; wave_pairs hands every butterfly's
+// register pair and twiddle index to bfly(rho0, rho1, wi), stage by stage from stage SP0 (forward:
+// high bit first; INV: low bit first).
+template <int RK, int LO, int PAT, bool INV, int SP0, class F>
+__device__ __forceinline__ void wave_pairs(uint32_t t, F&& bfly) {
   auto xof = [&](int rho) -> uint32_t {
     if (PAT == 0) return t + 32u * rho;
     if (PAT == 1) return ((t >> 2) << 5) | ((uint32_t)rho << 2) | (t & 3u);
@@ -454,26 +399,45 @@ __device__ __forceinline__ void prep_round(uint64_t (&e)[8], const ulonglong2* r
   constexpr int NPK = 1 << RK;
 #pragma unroll
   for (int sp = SP0; sp < RK; ++sp) {
-    const int bw = RK - 1 - sp, b = LO + bw, k = 7 - b, half = 1 << bw;
+    const int bw = INV ? sp : RK - 1 - sp, b = LO + bw, k = 7 - b, half = 1 << bw;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int grp = j / (NPK / 2), jj = j % (NPK / 2);
       const int rho0 = grp * NPK + ((jj >> bw) << (bw + 1)) + (jj & (half - 1));
-      const ulonglong2 w = roots[(1u << k) + (xof(rho0) >> (b + 1))];  // the limb's table, staged in LDS
-      // Harvey with a 4q-wide twiddle product: values in [0, 8q) (ring primes < 2^61), x
-      // reduced to [0, 4q), t = y w - Q' q in [0, 4q) with Q' the Shoup quotient less the low
-      // cross products (Q - 2 <= Q' <= Q): three 32-bit multiplies for the quotient, not four
-      // x >= 4q ? x - 4q : x, on the borrow (q2 = 4q here); LAZY (36 q < 2^64): x unreduced, each
-      // stage widens the bound by 4q, [0, 8q) after stage 0 -> [0, 36q) after stage 7
-      const uint64_t x = LAZY ? e[rho0] : canon_x(e[rho0], q2);
-      const uint64_t y = e[rho0 + half];
-      const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32), p0 = (uint32_t)w.y, p1 = (uint32_t)(w.y >> 32);
-      const uint64_t qa = mad64(y1, p1, __umulhi(y1, p0)) + __umulhi(y0, p1);
-      const uint64_t tt = y * w.x - qa * q;
-      e[rho0] = x + tt;
-      e[rho0 + half] = x + q2 - tt;
+      bfly(rho0, rho0 + half, (1u << k) + (xof(rho0) >> (b + 1)));
     }
   }
+}
+
+// Between rounds the points move through the wave's 288-word LDS row at `row` (ntt64.hpp's ROW
+// index algebra with hi = 0): lane t's offsets for the H pattern (+ 36 y padded, + 33 y or + 32 y
+// natural order), the M pattern (+ 4 y, + (y >> 1) padded) and the L pattern (9 t + r padded,
+// 8 t + (t >> 2) + r)
+struct WaveRows {
+  uint32_t H, M, L9, L8;
+};
+__device__ __forceinline__ WaveRows wave_rows(uint32_t row, uint32_t t) {
+  return WaveRows{row + t, row + 36 * (t >> 2) + (t & 3), row + 9 * t, row + 8 * t + (t >> 2)};
+}
+
+template <int RK, int LO, int PAT, int SP0 = 0, bool LAZY = false>
+__device__ __forceinline__ void prep_round(uint64_t (&e)[8], const ulonglong2* roots, uint64_t q, uint64_t q2,
+                                           uint32_t t) {
+  wave_pairs<RK, LO, PAT, false, SP0>(t, [&](int rho0, int rho1, uint32_t wi) {
+    const ulonglong2 w = roots[wi];  // the limb's table, staged in LDS
+    // Harvey with a 4q-wide twiddle product: values in [0, 8q) (ring primes < 2^61), x
+    // reduced to [0, 4q), t = y w - Q' q in [0, 4q) with Q' the Shoup quotient less the low
+    // cross products (Q - 2 <= Q' <= Q): three 32-bit multiplies for the quotient, not four
+    // x >= 4q ? x - 4q : x, on the borrow (q2 = 4q here); LAZY (36 q < 2^64): x unreduced, each
+    // stage widens the bound by 4q, [0, 8q) after stage 0 -> [0, 36q) after stage 7
+    const uint64_t x = LAZY ? e[rho0] : canon_x(e[rho0], q2);
+    const uint64_t y = e[rho1];
+    const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32), p0 = (uint32_t)w.y, p1 = (uint32_t)(w.y >> 32);
+    const uint64_t qa = mad64(y1, p1, __umulhi(y1, p0)) + __umulhi(y0, p1);
+    const uint64_t tt = y * w.x - qa * q;
+    e[rho0] = x + tt;
+    e[rho1] = x + q2 - tt;
+  });
 }
 
 // y w mod q in [0, 3q) for any 64-bit y: prep_round's Shoup product with the 3-multiply quotient
@@ -548,8 +512,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void prep256_kernel(PrepArgs a) {
     for (int k = (int)lane; k < nq * 256; k += 64) dst[k] = 0;
     return;
   }
-  const uint32_t rH = 288 * hs + t, rM = 288 * hs + 36 * (t >> 2) + (t & 3), rL9 = 288 * hs + 9 * t,
-                 rL8 = 288 * hs + 8 * t + (t >> 2);
+  const WaveRows wr = wave_rows(288 * hs, t);
   auto pair = [&](const int l0) {
     const int limb = l0 + (int)hs;
     const bool active = limb < nq;
@@ -610,27 +573,27 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void prep256_kernel(PrepArgs a) {
     // NTT: H round (stages 1-2; 0 above), H->M, M round (3-5), M->L, L round (6-7), L->H, store
     prep_round<3, 5, 0, 1, LAZY>(e, roots, q, q2, t);
 #pragma unroll
-    for (int y = 0; y < 8; ++y) lds[rH + 36 * y] = e[y];
+    for (int y = 0; y < 8; ++y) lds[wr.H + 36 * y] = e[y];
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) e[y] = lds[rM + 4 * y];
+    for (int y = 0; y < 8; ++y) e[y] = lds[wr.M + 4 * y];
     prep_round<3, 2, 1, 0, LAZY>(e, roots, q, q2, t);
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) lds[rM + 4 * y + (y >> 1)] = e[y];
+    for (int y = 0; y < 8; ++y) lds[wr.M + 4 * y + (y >> 1)] = e[y];
     wave_lds_fence();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) e[r] = lds[rL9 + r];
+    for (int r = 0; r < 8; ++r) e[r] = lds[wr.L9 + r];
     prep_round<2, 0, 2, 0, LAZY>(e, roots, q, q2, t);
     wave_lds_fence();
 #pragma unroll
     for (int r = 0; r < 8; ++r)  // [0, 8q) (LAZY: [0, 36q), Shoup by 1) -> [0, q)
-      lds[rL8 + r] = LAZY ? shoup_mul(e[r], 1, P.one_sh, q) : canon_x(canon_x(canon_x(e[r], q2), 2 * q), q);
+      lds[wr.L8 + r] = LAZY ? shoup_mul(e[r], 1, P.one_sh, q) : canon_x(canon_x(canon_x(e[r], q2), 2 * q), q);
     wave_lds_fence();
     if (active) {
       uint64_t* o = dst + (long long)limb * 256;
 #pragma unroll
-      for (int y = 0; y < 8; ++y) o[t + 32 * y] = lds[rH + 33 * y];
+      for (int y = 0; y < 8; ++y) o[t + 32 * y] = lds[wr.H + 33 * y];
     }
     wave_lds_fence();
   };
@@ -647,57 +610,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void prep256_kernel(PrepArgs a) {
 // ------------------------------------------------------------------------------------------
 // 3. multiply-accumulate (inner / outer Ajtai products)
 // ------------------------------------------------------------------------------------------
-struct MacArgs {
-  int d, nl, J;            // degree, limbs, outputs per column
-  long long ncols;         // B * columns
-  int T1, T2;              // terms from operand set 1 / 2
-  const uint64_t* A1;      // [J][T1][nl][d]   commit key
-  const uint64_t* B1;      // [ncols][T1][nl][d] (stride b1_col per column, b1_term per term)
-  long long b1_col, b1_term;
-  const uint64_t* A2;      // [J][T2][nl][d]
-  const uint64_t* B2;
-  long long b2_col, b2_term;
-  const uint64_t* C;       // added after reduction: [ncols][...] + j * c_j  (nullable)
-  long long c_col, c_j;
-  uint64_t* out;           // [ncols][J][nl][d]
-  RnsPrime P[kMaxQ];
-};
-
-// acc += a * b as an exact multiword sum; WIDE keeps a third word (needed only when
-// (q-1)^2 * terms could reach 2^128: decided per launch on the host).
-template <bool WIDE>
-struct Acc {
-  uint64_t lo, hi;
-  uint32_t top;
-  __device__ __forceinline__ void zero() {
-    lo = hi = 0;
-    top = 0;
-  }
-  __device__ __forceinline__ void mac(uint64_t a, uint64_t b) {
-    uint64_t pl, ph;
-    mul_wide(a, b, pl, ph);
-    uint32_t c = 0;
-    lo = addc(lo, pl, c);
-    if constexpr (WIDE) {
-      uint32_t c2 = 0;
-      hi = addc(hi, ph, c2);
-      uint32_t c3 = 0;
-      hi = addc(hi, (uint64_t)c, c3);
-      top += c2 + c3;
-    } else {
-      hi += ph + c;
-    }
-  }
-  // (lo + hi 2^64 + top 2^128) * 2^-64 mod q = lo 2^-64 + hi + top 2^64
-  __device__ __forceinline__ uint64_t reduce(const RnsPrime& P) const {
-    const uint64_t q = P.q;
-    uint64_t r = sh_mul(lo, P.rinv, P.rinv_sh, q);
-    r = mod_add(r, sh_mul(hi, 1, P.one_sh, q), q);
-    if constexpr (WIDE) r = mod_add(r, sh_mul((uint64_t)top, P.r64, P.r64_sh, q), q);
-    return r;
-  }
-};
-
 // Thread = (column group of NC columns, limb*coeff).  Per term: JB commit-key words are loaded
 // once and reused for NC columns, NC data words reused for JB outputs (register tiling of the
 // per-(limb, coeff) modular GEMM  out[j][col] = sum_t A[j][t] B[t][col]).
@@ -780,7 +692,7 @@ static rg_status launch_mac_w(const MacArgs& m, int jb, int j0, hipStream_t st) 
 }
 
 // J outputs split into ceil(J/8) launches of equal width
-static rg_status launch_mac(const MacArgs& m, hipStream_t st) {
+rg_status launch_mac(const MacArgs& m, hipStream_t st) {
   uint64_t qmax = 0;
   for (int l = 0; l < m.nl; ++l) qmax = std::max(qmax, m.P[l].q);
   const double bits = 2.0 * log2((double)(qmax - 1)) + log2((double)(m.T1 + m.T2) + 1.0);
@@ -791,79 +703,13 @@ static rg_status launch_mac(const MacArgs& m, hipStream_t st) {
   return RG_OK;
 }
 
-
 // ------------------------------------------------------------------------------------------
 // 4. round: IMForm -> INTT -> centred CRT -> floor shift -> mod q' -> MForm -> NTT
 // ------------------------------------------------------------------------------------------
-struct RoundArgs {
-  int d, cut;
-  RingDev src, dst;
-  CrtDev crt;
-  DstDev dm;
-  const uint64_t* in;  // [npoly][src.n][d]
-  uint64_t* out;       // [npoly] at stride out_stride, dst.n limbs (+ zero rows up to out_rows)
-  long long out_stride;
-  int out_rows;
-  long long npoly;     // round256_kernel's polynomials (round_kernel: the grid)
-};
-
-__device__ __forceinline__ void mw_muladd(uint64_t* v, int nw, uint64_t m, uint64_t add) {
-  uint64_t carry = add;
-  for (int i = 0; i < nw; ++i) {
-    uint64_t lo, hi;
-    mul_wide(v[i], m, lo, hi);
-    uint32_t c = 0;
-    lo = addc(lo, carry, c);
-    v[i] = lo;
-    carry = hi + c;
-  }
-}
-
-// reconstructTo (rns.go:76-105) of one coefficient's residues r[ns] (coefficient domain): the
-// centred value as sign (returned) and 4-word magnitude
-__device__ __forceinline__ bool crt_centred(const CrtDev& crt, int ns, const uint64_t* r, uint64_t mag[4]) {
-  bool neg;
-  mag[0] = mag[1] = mag[2] = mag[3] = 0;
-  if (ns == 1) {  // reconstructTo fast path: toBalanced (rns.go:68-73,78-91)
-    const uint64_t q = crt.q[0];
-    neg = r[0] > (q >> 1);
-    mag[0] = neg ? q - r[0] : r[0];
-  } else {  // Garner: V = x0 + q0 (x1 + q1 (x2 + ...)) in [0, Q)  (rns.go:93-99)
-    uint64_t x[kMaxQ];
-    for (int j = 0; j < ns; ++j) {
-      const uint64_t qj = crt.q[j];
-      uint64_t v = r[j];
-      for (int kk = 0; kk < j; ++kk) {
-        uint64_t xk = x[kk];
-        // x_k < q_k must be below q_j for mod_sub: one subtraction where q_k < 2 q_j (primes of
-        // one bit size, every NewParameters ring), x_k % q_j for any other pair of primes
-        if (xk >= qj) xk = (xk - qj >= qj) ? xk % qj : xk - qj;
-        v = mod_sub(v, xk, qj);
-        v = sh_mul(v, crt.inv[j][kk], crt.inv_sh[j][kk], qj);
-      }
-      x[j] = v;
-    }
-    uint64_t V[4] = {x[ns - 1], 0, 0, 0};
-    for (int j = ns - 2; j >= 0; --j) mw_muladd(V, 4, crt.q[j], x[j]);
-    // V >= floor(Q/2) -> V - Q (rns.go:100-102)
-    bool ge = true;
-    for (int i = 3; i >= 0; --i) {
-      if (V[i] != crt.Qhalf[i]) {
-        ge = V[i] > crt.Qhalf[i];
-        break;
-      }
-    }
-    neg = ge;
-    if (neg) {
-      uint32_t br = 0;
-      for (int i = 0; i < 4; ++i) mag[i] = subb(crt.Q[i], V[i], br);
-    } else {
-      for (int i = 0; i < 4; ++i) mag[i] = V[i];
-    }
-  }
-  return neg;
-}
-
+// The rounding tail of one coefficient (floor shift by the cut with the toward-minus-infinity fix,
+// the zero test, the Euclidean residue per destination prime, MForm) is written out in both round
+// kernels: change the two copies together.  (One __forceinline__ helper compiles to different code
+// in both: profiles/r08b_jindo_split_commit_ab.txt.)
 __global__ __launch_bounds__(256) void round_kernel(RoundArgs a) {
   // LDS sized per launch (max(ns, nd) limbs x d words), not for kMaxQ x kMaxD: occupancy is then
   // register-limited (7 waves/SIMD) instead of LDS-limited (5)
@@ -927,7 +773,6 @@ __global__ __launch_bounds__(256) void round_kernel(RoundArgs a) {
   for (int k = tid; k < a.out_rows * d; k += blockDim.x) out[k] = (k / d < nd) ? poly(k / d)[k % d] : 0;
 }
 
-
 // Wave-per-polynomial round for d = 256 (every Jindo shape): one wave owns one polynomial, a
 // limb pair at a time in its two half-waves (lanes 0-31 limb l0, 32-63 limb l0 + 1), 8 points per
 // lane in registers.  The inverse and forward 256-point transforms run as rounds of 3 + 3 + 2
@@ -938,26 +783,13 @@ __global__ __launch_bounds__(256) void round_kernel(RoundArgs a) {
 constexpr int kRoundWaves = 4;
 template <int RK, int LO, int PAT, bool INV>
 __device__ __forceinline__ void wround(uint64_t (&e)[8], const ulonglong2* roots, const Q64& Q, uint32_t t) {
-  auto xof = [&](int rho) -> uint32_t {
-    if (PAT == 0) return t + 32u * rho;
-    if (PAT == 1) return ((t >> 2) << 5) | ((uint32_t)rho << 2) | (t & 3u);
-    return 8u * t + rho;
-  };
-  constexpr int NPK = 1 << RK;
-#pragma unroll
-  for (int sp = 0; sp < RK; ++sp) {
-    const int bw = INV ? sp : RK - 1 - sp, b = LO + bw, k = 7 - b, half = 1 << bw;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int grp = j / (NPK / 2), jj = j % (NPK / 2);
-      const int rho0 = grp * NPK + ((jj >> bw) << (bw + 1)) + (jj & (half - 1)), rho1 = rho0 + half;
-      const ulonglong2 w = roots[(1u << k) + (xof(rho0) >> (b + 1))];
-      if constexpr (INV)
-        inv_bfly_lazy<false>(e[rho0], e[rho1], w.x, w.y, Q);
-      else
-        fwd_bfly_lazy<false>(e[rho0], e[rho1], w.x, w.y, Q);
-    }
-  }
+  wave_pairs<RK, LO, PAT, INV, 0>(t, [&](int rho0, int rho1, uint32_t wi) {
+    const ulonglong2 w = roots[wi];
+    if constexpr (INV)
+      inv_bfly_lazy<false>(e[rho0], e[rho1], w.x, w.y, Q);
+    else
+      fwd_bfly_lazy<false>(e[rho0], e[rho1], w.x, w.y, Q);
+  });
 }
 
 __global__ __launch_bounds__(64 * kRoundWaves) void round256_kernel(RoundArgs a) {
@@ -981,29 +813,29 @@ __global__ __launch_bounds__(64 * kRoundWaves) void round256_kernel(RoundArgs a)
     const Q64 Q = make_q64(P.q);
     const ulonglong2* roots = rtab + lc * 256;
     const uint32_t row = 288u * (uint32_t)(l0 + (int)hs);
-    const uint32_t rH = row + t, rM = row + 36 * (t >> 2) + (t & 3), rL9 = row + 9 * t, rL8 = row + 8 * t + (t >> 2);
+    const WaveRows wr = wave_rows(row, t);
     uint64_t e[8];
 #pragma unroll
     for (int y = 0; y < 8; ++y) e[y] = sh_mul(in[lc * 256 + t + 32 * y], P.rinv, P.rinv_sh, P.q);
 #pragma unroll
-    for (int y = 0; y < 8; ++y) wl[rH + 33 * y] = e[y];  // H -> L (pad x >> 5)
+    for (int y = 0; y < 8; ++y) wl[wr.H + 33 * y] = e[y];  // H -> L (pad x >> 5)
     wave_lds_fence();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) e[r] = wl[rL8 + r];
+    for (int r = 0; r < 8; ++r) e[r] = wl[wr.L8 + r];
     wround<2, 0, 2, true>(e, roots, Q, t);
     wave_lds_fence();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) wl[rL9 + r] = e[r];  // L -> M
+    for (int r = 0; r < 8; ++r) wl[wr.L9 + r] = e[r];  // L -> M
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) e[y] = wl[rM + 4 * y + (y >> 1)];
+    for (int y = 0; y < 8; ++y) e[y] = wl[wr.M + 4 * y + (y >> 1)];
     wround<3, 2, 1, true>(e, roots, Q, t);
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) wl[rM + 4 * y] = e[y];  // M -> H
+    for (int y = 0; y < 8; ++y) wl[wr.M + 4 * y] = e[y];  // M -> H
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) e[y] = wl[rH + 36 * y];
+    for (int y = 0; y < 8; ++y) e[y] = wl[wr.H + 36 * y];
     wround<3, 5, 0, true>(e, roots, Q, t);
     wave_lds_fence();
 #pragma unroll
@@ -1048,32 +880,32 @@ __global__ __launch_bounds__(64 * kRoundWaves) void round256_kernel(RoundArgs a)
     const Q64 Q = make_q64(a.dst.p[lc].q);
     const ulonglong2* roots = rtab + (ns + lc) * 256;
     const uint32_t row = 288u * (uint32_t)(l0 + (int)hs);
-    const uint32_t rH = row + t, rM = row + 36 * (t >> 2) + (t & 3), rL9 = row + 9 * t, rL8 = row + 8 * t + (t >> 2);
+    const WaveRows wr = wave_rows(row, t);
     uint64_t e[8];
 #pragma unroll
     for (int y = 0; y < 8; ++y) e[y] = wl[288 * lc + t + 32 * y];
     wave_lds_fence();
     wround<3, 5, 0, false>(e, roots, Q, t);
 #pragma unroll
-    for (int y = 0; y < 8; ++y) wl[rH + 36 * y] = e[y];  // H -> M
+    for (int y = 0; y < 8; ++y) wl[wr.H + 36 * y] = e[y];  // H -> M
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) e[y] = wl[rM + 4 * y];
+    for (int y = 0; y < 8; ++y) e[y] = wl[wr.M + 4 * y];
     wround<3, 2, 1, false>(e, roots, Q, t);
     wave_lds_fence();
 #pragma unroll
-    for (int y = 0; y < 8; ++y) wl[rM + 4 * y + (y >> 1)] = e[y];  // M -> L
+    for (int y = 0; y < 8; ++y) wl[wr.M + 4 * y + (y >> 1)] = e[y];  // M -> L
     wave_lds_fence();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) e[r] = wl[rL9 + r];
+    for (int r = 0; r < 8; ++r) e[r] = wl[wr.L9 + r];
     wround<2, 0, 2, false>(e, roots, Q, t);
     wave_lds_fence();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) wl[rL8 + r] = canon(e[r], Q);  // L -> H, canonical
+    for (int r = 0; r < 8; ++r) wl[wr.L8 + r] = canon(e[r], Q);  // L -> H, canonical
     wave_lds_fence();
     if (limb < nd) {
 #pragma unroll
-      for (int y = 0; y < 8; ++y) out[limb * 256 + t + 32 * y] = wl[rH + 33 * y];
+      for (int y = 0; y < 8; ++y) out[limb * 256 + t + 32 * y] = wl[wr.H + 33 * y];
     }
     wave_lds_fence();
   }
@@ -2009,258 +1841,10 @@ __global__ __launch_bounds__(512) void uniform_words_kernel(AesKey key, const ui
   u.init(kl, lds, inst);
   out[gid] = u.word_at(first + (unsigned long long)gid);
 }
-// ------------------------------------------------------------------------------------------
-// 7. Verifier.Verify (verifier.go:50-282), challenges injected.  The MACs run on mac_kernel,
-// the lifted inner commitments on round_kernel (cut 0, ringQOut -> ringQ); these kernels add:
-//   norm_kernel    workgroup per polynomial: IMForm, INTT, centred CRT, sum of squares
-//                  (verifyNorm :262-276) -> kNormW words per polynomial
-//   combine_kernel A * 2^cut - B per residue (MulRNSScalarMontgomery, ...ThenSub)
-//   neq_kernel     any word of x != y -> flag (verifyConsistency :203-221)
-//   decode_kernel  workgroup per polynomial: IMForm, INTT, centred CRT, SetBigInt mod p,
-//                  Horner in base b over the slots (DecodeTo, encoder.go:203-219)
-//   dot2_kernel    one workgroup: sum right * dcd and sum batchDcd[0] * y (verifyEval :224-259)
-// ------------------------------------------------------------------------------------------
-constexpr int kNormW = 10;  // words of a sum of squares (|value| < 2^240, <= 2^20 values)
-
-struct NormArgs {
-  int d;
-  RingDev R;
-  CrtDev crt;
-  const uint64_t* in;  // [npoly] at stride in_stride, R.n limbs
-  long long in_stride;
-  uint64_t* out;       // [npoly][kNormW]
-};
-
-__device__ __forceinline__ void mw_add(uint64_t* a, const uint64_t* b, int n) {
-  uint32_t c = 0;
-  for (int i = 0; i < n; ++i) a[i] = addc(a[i], b[i], c);
-}
-
-__global__ __launch_bounds__(256) void norm_kernel(NormArgs a) {
-  extern __shared__ uint64_t poly_lds[];
-  const int d = a.d, tid = threadIdx.x, ns = a.R.n;
-  auto poly = [&](int l) { return poly_lds + (long long)l * d; };
-  const long long pid = blockIdx.x;
-  const uint64_t* in = a.in + pid * a.in_stride;
-  for (int k = tid; k < ns * d; k += blockDim.x) {
-    const int l = k / d;
-    const RnsPrime& P = a.R.p[l];
-    poly(l)[k % d] = sh_mul(in[k], P.rinv, P.rinv_sh, P.q);  // IMForm
-  }
-  __syncthreads();
-  const int half = blockDim.x >> 1;
-  for (int l0 = 0; l0 < ns; l0 += 2) {
-    const int l = l0 + (tid >= half ? 1 : 0);
-    const bool active = l < ns;
-    const int lc = active ? l : l0;
-    intt_lds(poly(lc), d, a.R.bwd + (long long)lc * d, a.R.p[lc], tid % half, half, active);
-  }
-  uint64_t acc[kNormW];
-  for (int i = 0; i < kNormW; ++i) acc[i] = 0;
-  for (int k = tid; k < d; k += blockDim.x) {
-    uint64_t r[kMaxQ], mag[4];
-    for (int l = 0; l < ns; ++l) r[l] = poly(l)[k];
-    crt_centred(a.crt, ns, r, mag);
-    uint64_t sq[kNormW];
-    for (int i = 0; i < kNormW; ++i) sq[i] = 0;
-    for (int i = 0; i < 4; ++i) {
-      uint64_t carry = 0;
-      for (int j = 0; j < 4; ++j) {
-        uint64_t lo, hi;
-        mul_wide(mag[i], mag[j], lo, hi);
-        uint32_t c = 0;
-        lo = addc(lo, sq[i + j], c);
-        hi += c;
-        c = 0;
-        lo = addc(lo, carry, c);
-        hi += c;
-        sq[i + j] = lo;
-        carry = hi;
-      }
-      sq[i + 4] += carry;
-    }
-    mw_add(acc, sq, kNormW);
-  }
-  __syncthreads();  // poly_lds is reused for the reduction
-  for (int i = 0; i < kNormW; ++i) poly_lds[tid * kNormW + i] = acc[i];
-  __syncthreads();
-  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-    if (tid < s) mw_add(poly_lds + tid * kNormW, poly_lds + (tid + s) * kNormW, kNormW);
-    __syncthreads();
-  }
-  if (tid < kNormW) a.out[pid * kNormW + tid] = poly_lds[tid];
-}
-
-// out[p][l][k] = A[p][l][k] * c_l - B[p][l][k] mod q_l  (A, B, out: [npoly][nl][d] contiguous)
-__global__ __launch_bounds__(256) void combine_kernel(const uint64_t* A, const uint64_t* B, uint64_t* out,
-                                                      long long n, int nl, int d, RingDev R, uint64_t c0,
-                                                      uint64_t c1, uint64_t c2, uint64_t c3) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int l = (int)((i / d) % nl);
-  const RnsPrime& P = R.p[l];
-  const uint64_t c = l == 0 ? c0 : l == 1 ? c1 : l == 2 ? c2 : c3;
-  const uint64_t cp = (uint64_t)(((unsigned __int128)c << 64) / P.q);
-  out[i] = mod_sub(sh_mul(A[i], c, cp, P.q), B[i], P.q);
-}
-
-__global__ __launch_bounds__(256) void neq_kernel(const uint64_t* x, const uint64_t* y, long long n, int* flag) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && x[i] != y[i]) atomicOr(flag, 1);
-}
-
-template <int L>
-struct DecodeArgs {
-  int d, slots, exp, nout;
-  RingDev R;
-  CrtDev crt;
-  FieldParams<L> F;
-  uint64_t pw[4][L];  // 2^(64 i) R^2 mod p: montmul(w, pw[i]) = w 2^(64 i) R
-  uint64_t bmont[L];  // base in Montgomery form
-  const uint64_t* in;  // [npoly][R.n][d]
-  uint64_t* out;       // [npoly][nout][L]
-};
-
-template <int L>
-__global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<L> a) {
-  extern __shared__ uint64_t poly_lds[];  // R.n * d words, then d * L words of coefficients
-  const int d = a.d, tid = threadIdx.x, ns = a.R.n;
-  auto poly = [&](int l) { return poly_lds + (long long)l * d; };
-  uint64_t* ce = poly_lds + (long long)ns * d;
-  const long long pid = blockIdx.x;
-  const uint64_t* in = a.in + pid * ns * d;
-  for (int k = tid; k < ns * d; k += blockDim.x) {
-    const int l = k / d;
-    const RnsPrime& P = a.R.p[l];
-    poly(l)[k % d] = sh_mul(in[k], P.rinv, P.rinv_sh, P.q);  // IMForm
-  }
-  __syncthreads();
-  const int half = blockDim.x >> 1;
-  for (int l0 = 0; l0 < ns; l0 += 2) {
-    const int l = l0 + (tid >= half ? 1 : 0);
-    const bool active = l < ns;
-    const int lc = active ? l : l0;
-    intt_lds(poly(lc), d, a.R.bwd + (long long)lc * d, a.R.p[lc], tid % half, half, active);
-  }
-  for (int k = tid; k < d; k += blockDim.x) {  // reconstructTo, then SetBigInt (mod p)
-    uint64_t r[kMaxQ], mag[4];
-    for (int l = 0; l < ns; ++l) r[l] = poly(l)[k];
-    const bool neg = crt_centred(a.crt, ns, r, mag);
-    uint64_t v[L], t[L], w[L];
-#pragma unroll
-    for (int i = 0; i < L; ++i) v[i] = 0;
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int j = 0; j < L; ++j) w[j] = j == 0 ? mag[i] : 0;
-      if (L == 1) w[0] = mag[i] % a.F.q[0];  // a word may exceed a one-limb p
-      f_mul<L>(t, w, a.pw[i], a.F);
-      f_add<L>(v, v, t, a.F);
-    }
-    if (neg) f_neg<L>(v, v, a.F);
-#pragma unroll
-    for (int j = 0; j < L; ++j) ce[(long long)k * L + j] = v[j];
-  }
-  __syncthreads();
-  for (int i = tid; i < a.nout; i += blockDim.x) {  // Horner over j = exp-1 .. 0
-    uint64_t v[L];
-#pragma unroll
-    for (int j = 0; j < L; ++j) v[j] = 0;
-    for (int j = a.exp - 1; j >= 0; --j) {
-      f_mul<L>(v, v, a.bmont, a.F);
-      f_add<L>(v, v, ce + (long long)(j * a.slots + i) * L, a.F);
-    }
-#pragma unroll
-    for (int j = 0; j < L; ++j) a.out[(pid * a.nout + i) * L + j] = v[j];
-  }
-}
-
-// one workgroup: out[0] = sum_i x1[i] * y1[i] (n1 terms), out[1] = sum_i x2[i] * y2[i] (n2)
-template <int L>
-__global__ __launch_bounds__(256) void dot2_kernel(FieldParams<L> F, const uint64_t* x1, const uint64_t* y1,
-                                                   long long n1, const uint64_t* x2, const uint64_t* y2, long long n2,
-                                                   uint64_t* out) {
-  __shared__ uint64_t red[256 * L];
-  for (int which = 0; which < 2; ++which) {
-    const uint64_t* x = which ? x2 : x1;
-    const uint64_t* y = which ? y2 : y1;
-    const long long n = which ? n2 : n1;
-    uint64_t acc[L], t[L];
-#pragma unroll
-    for (int j = 0; j < L; ++j) acc[j] = 0;
-    for (long long i = threadIdx.x; i < n; i += blockDim.x) {
-      f_mul<L>(t, x + i * L, y + i * L, F);
-      f_add<L>(acc, acc, t, F);
-    }
-#pragma unroll
-    for (int j = 0; j < L; ++j) red[threadIdx.x * L + j] = acc[j];
-    __syncthreads();
-    for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) f_add<L>(red + threadIdx.x * L, red + threadIdx.x * L, red + (threadIdx.x + s) * L, F);
-      __syncthreads();
-    }
-    if (threadIdx.x < L) out[which * L + threadIdx.x] = red[threadIdx.x];
-    __syncthreads();
-  }
-}
-}  // namespace rg
 
 // ------------------------------------------------------------------------------------------
-// host
+// host (the handle and its per-stream scratch: jindo_impl.hpp)
 // ------------------------------------------------------------------------------------------
-// Scratch of one commit stream: digits [B][cols+1][rows][d] u32, inner commitments
-// [B][cols+1][inMSIS][nq][d], outer [B][outMSIS][nqo][d].  One per stream, so calls on
-// different streams never share scratch (calls on one stream are ordered by the stream).
-struct rg_jindo_scratch {
-  rg::DevBuf digits, com, ocom;
-  rg::DevBuf last, mask, en, mn;  // the sampled randomness of rg_jindo_commit_sampled_dev
-  rg::DevBuf wq;                  // cdt2_noise_kernel's chunk counter
-};
-
-// Sampler setup (rg_jindo_set_stddevs): the reference's six standard deviations and the tables
-// derived from them on the host (csprng_host.hpp)
-struct rg_jindo_samplers {
-  bool ready = false;
-  double sd[6];  // ecd, ecd_blind, mask, mask_blind, mlwe, mask_mlwe
-  rg::DevBuf te0, cdt_enc, cdt_guide, cdt_sbound, cdt_jmax, cdt_mlwe, zig, delta;
-  int cdt_enc_size = 0, cdt_mlwe_size = 0;
-  int64_t tail_lo_enc = 0, tail_lo_mlwe = 0;
-  std::vector<double> h_delta;
-};
-
-struct rg_jindo {
-  rg_jindo_params p;
-  rg_field field;
-  int device = 0;  // the handle's buffers live on this device
-  rg::RnsPrime rq[rg::kMaxQ], ro[rg::kMaxQ];
-  rg::DevBuf rootsq_f, rootsq_b, rootso_f, rootso_b;
-  rg::CrtDev crt_q, crt_o;
-  rg::DstDev dst_o, dst_q;
-  rg::DevBuf ck_in, ck_mlwe, ck_out;  // the commit key, device-resident (entities.go:21-73 layouts)
-  rg::DevBuf ckm_in, ckm_out;  // the same as base-256 digits for mac_mfma (inner, outer)
-  int mfma_q = 0, mfma_o = 0;  // digits per residue of the MFMA MAC (0: mac_kernel)
-  uint64_t base_inv;
-  std::mutex mu;  // guards `scratch` and `aux`
-  std::map<hipStream_t, std::unique_ptr<rg_jindo_scratch>> scratch;
-  rg_jindo_samplers smp;
-  // the sampled commit's helper streams and events, one set per caller stream (lazily created):
-  // s[0] runs the COSAC centres + cosac2, s[1] the MLWE samplers and their prep (commit_sampled_dev)
-  struct Aux {
-    hipStream_t s[2] = {nullptr, nullptr};
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  };
-  std::map<hipStream_t, Aux> aux;
-  ~rg_jindo() {
-    for (auto& kv : aux) {
-      for (hipStream_t x : kv.second.s)
-        if (x) (void)hipStreamDestroy(x);
-      for (hipEvent_t x : kv.second.e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  }
-};
-
-namespace rg {
-
 // ring.PrimitiveRoot: smallest g >= 3 that generates Z_q^* (factors by trial division +
 // Pollard rho; q < 2^62)
 static bool is_prime_u64(uint64_t n) {
@@ -2408,7 +1992,7 @@ static void make_dst(const uint64_t* primes, int n, DstDev& D) {
   }
 }
 
-static RingDev ring_dev(const RnsPrime* P, int n, const DevBuf& f, const DevBuf& b) {
+RingDev ring_dev(const RnsPrime* P, int n, const DevBuf& f, const DevBuf& b) {
   RingDev R;
   memset(&R, 0, sizeof(R));
   R.n = n;
@@ -2482,8 +2066,7 @@ static rg_status launch_digits(const rg_jindo* J, size_t batch, const uint64_t* 
                                const uint64_t* mask, uint32_t* digits, hipStream_t st) {
   DigitArgs<L> a;
   a.s = shape_of(J->p, nv);
-  memcpy(a.F.q, J->field.q, 8 * L);
-  a.F.qinv = J->field.qinv;
+  a.F = field_params<L>(&J->field);
   a.base_inv = J->base_inv;
   const uint64_t b2 = (uint64_t)J->p.base * J->p.base;
   a.b2 = (b2 >> 32) ? 0 : b2;
@@ -2554,7 +2137,7 @@ static MfmaMacArgs mfma_args(const MacArgs& m, const DevBuf& key) {
 }
 
 // A handle's buffers belong to the device it was created on
-static rg_status on_device(const rg_jindo* J) {
+rg_status on_device(const rg_jindo* J) {
   int cur = -1;
   RG_HIP(hipGetDevice(&cur));
   if (cur != J->device) {
@@ -2565,12 +2148,30 @@ static rg_status on_device(const rg_jindo* J) {
   return RG_OK;
 }
 
-// The deterministic Ajtai core (prover.go:144-202) over a batch of NTT-domain openings:
-// inner MAC, rounding into Opening.InCommit, outer MAC and rounding into Commitment.Value.
+RoundArgs round_args(const rg_jindo* J, bool src_o, bool dst_o, int cut, const uint64_t* in, uint64_t* out,
+                     long long out_stride, int out_rows) {
+  auto ring = [&](bool o) {
+    return o ? ring_dev(J->ro, J->p.nqo, J->rootso_f, J->rootso_b) : ring_dev(J->rq, J->p.nq, J->rootsq_f, J->rootsq_b);
+  };
+  RoundArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.d = J->p.d;
+  ra.cut = cut;
+  ra.src = ring(src_o);
+  ra.dst = ring(dst_o);
+  ra.crt = src_o ? J->crt_o : J->crt_q;
+  ra.dm = dst_o ? J->dst_o : J->dst_q;
+  ra.in = in;
+  ra.out = out;
+  ra.out_stride = out_stride;
+  ra.out_rows = out_rows;
+  return ra;
+}
+
 // CRT rounding of `npoly` polynomials: round256_kernel (a wave per polynomial) for d = 256 and
 // primes below 2^62 (its lazy butterflies need 2q < 2^63), round_kernel otherwise.  round256
 // against round_kernel at configs[4]: 429 vs 513 us per launch (profiles/r05s_round_wave_ab.txt)
-static rg_status launch_round(RoundArgs ra, long long npoly, hipStream_t st) {
+rg_status launch_round(RoundArgs ra, long long npoly, hipStream_t st) {
   ra.npoly = npoly;
   bool small = ra.d == 256;
   for (int l = 0; l < ra.src.n; ++l) small = small && ra.src.p[l].q < (1ull << 62);
@@ -2587,96 +2188,58 @@ static rg_status launch_round(RoundArgs ra, long long npoly, hipStream_t st) {
   return check_launch("jindo round");
 }
 
+// The deterministic Ajtai core (prover.go:144-202) over a batch of NTT-domain openings:
+// inner MAC, rounding into Opening.InCommit, outer MAC and rounding into Commitment.Value.
 static rg_status commit_core(rg_jindo* J, size_t batch, const uint64_t* d_enc, const uint64_t* d_mlwe,
                              uint64_t* d_incom, uint64_t* d_com, rg_jindo_scratch* sc, hipStream_t st) {
   const rg_jindo_params& p = J->p;
-  const int d = p.d, nq = p.nq, nqo = p.nqo, nm = p.in_msis + p.mlwe;
-  // 3. inner MAC
-  MacArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.d = d;
-  ma.nl = nq;
+  const int nm = p.in_msis + p.mlwe;
+  const long long pq = (long long)p.nq * p.d, po = (long long)p.nqo * p.d;
+  // 3. inner MAC: sum_k In[j][k] Enc[k] + sum_k CK.MLWE[j][k] MLWE[k] + MLWE[mlwe + j]
+  MacArgs ma = dot_args(J->rq, p.nq, p.d, (long long)batch * (p.cols + 1), p.rows, J->ck_in.as<uint64_t>(), d_enc,
+                        p.rows * pq, pq, sc->com.as<uint64_t>());
   ma.J = p.in_msis;
-  ma.ncols = (long long)batch * (p.cols + 1);
-  ma.T1 = p.rows;
-  ma.A1 = J->ck_in.as<uint64_t>();
-  ma.B1 = d_enc;
-  ma.b1_col = (long long)p.rows * nq * d;
-  ma.b1_term = (long long)nq * d;
   ma.T2 = p.mlwe;
   ma.A2 = J->ck_mlwe.as<uint64_t>();
   ma.B2 = d_mlwe;
-  ma.b2_col = (long long)nm * nq * d;
-  ma.b2_term = (long long)nq * d;
-  ma.C = d_mlwe + (long long)p.mlwe * nq * d;  // MLWE[i][mlwe + j]
-  ma.c_col = (long long)nm * nq * d;
-  ma.c_j = (long long)nq * d;
-  ma.out = sc->com.as<uint64_t>();
-  for (int l = 0; l < nq; ++l) ma.P[l] = J->rq[l];
+  ma.b2_col = nm * pq;
+  ma.b2_term = pq;
+  ma.C = d_mlwe + p.mlwe * pq;  // MLWE[i][mlwe + j]
+  ma.c_col = nm * pq;
+  ma.c_j = pq;
   if (J->mfma_q) {
     RG_TRY(launch_mac_mfma(mfma_args(ma, J->ckm_in), J->mfma_q, st));
   } else {
     RG_TRY(launch_mac(ma, st));
   }
   // 4. inner round -> Opening.InCommit (column i, j -> index i*inMSIS + j)
-  RoundArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  ra.d = d;
-  ra.cut = p.log_in_cut;
-  ra.src = ring_dev(J->rq, nq, J->rootsq_f, J->rootsq_b);
-  ra.dst = ring_dev(J->ro, nqo, J->rootso_f, J->rootso_b);
-  ra.crt = J->crt_q;
-  ra.dm = J->dst_o;
-  ra.in = sc->com.as<uint64_t>();
-  ra.out = d_incom;
-  ra.out_stride = (long long)nqo * d;
-  ra.out_rows = nqo;
   {
     const long long npoly = (long long)batch * (p.cols + 1) * p.in_msis;  // == batch * dcmp, same order
-    RG_TRY(launch_round(ra, npoly, st));
+    RG_TRY(launch_round(round_args(J, false, true, p.log_in_cut, sc->com.as<uint64_t>(), d_incom, po, p.nqo), npoly,
+                        st));
   }
   // 5. outer MAC + round -> Commitment.Value (ringQ-shaped rows, rows >= nqo zero)
-  MacArgs mo;
-  memset(&mo, 0, sizeof(mo));
-  mo.d = d;
-  mo.nl = nqo;
+  MacArgs mo = dot_args(J->ro, p.nqo, p.d, (long long)batch, p.dcmp, J->ck_out.as<uint64_t>(), d_incom, p.dcmp * po, po,
+                        sc->ocom.as<uint64_t>());
   mo.J = p.out_msis;
-  mo.ncols = (long long)batch;
-  mo.T1 = p.dcmp;
-  mo.A1 = J->ck_out.as<uint64_t>();
-  mo.B1 = d_incom;
-  mo.b1_col = (long long)p.dcmp * nqo * d;
-  mo.b1_term = (long long)nqo * d;
-  mo.out = sc->ocom.as<uint64_t>();
-  for (int l = 0; l < nqo; ++l) mo.P[l] = J->ro[l];
   if (J->mfma_o) {
     RG_TRY(launch_mac_mfma(mfma_args(mo, J->ckm_out), J->mfma_o, st));
   } else {
     RG_TRY(launch_mac(mo, st));
   }
-  RoundArgs ro = ra;
-  ro.cut = p.log_out_cut;
-  ro.src = ring_dev(J->ro, nqo, J->rootso_f, J->rootso_b);
-  ro.crt = J->crt_o;
-  ro.in = sc->ocom.as<uint64_t>();
-  ro.out = d_com;
-  ro.out_stride = (long long)nq * d;
-  ro.out_rows = nq;
-  RG_TRY(launch_round(ro, (long long)batch * p.out_msis, st));
+  RG_TRY(launch_round(round_args(J, true, true, p.log_out_cut, sc->ocom.as<uint64_t>(), d_com, pq, p.nq),
+                      (long long)batch * p.out_msis, st));
   RG_TRY(check_launch("jindo round(out)"));
   return RG_OK;
 }
 
-// 1. digits of every encode's source elements into the stream's scratch
+// 1. digits of every encode's source elements into the stream's scratch.  (rg_jindo_create's
+// validate admits only the five limb counts, so dispatch_limbs' refusal is never reached here.)
 static rg_status digits_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, size_t nv, const uint64_t* d_last,
                               const uint64_t* d_mask, uint32_t* digits, hipStream_t st) {
-  switch (J->p.field_limbs) {
-    case 1: return launch_digits<1>(J, batch, d_v, (long long)nv, d_last, d_mask, digits, st);
-    case 2: return launch_digits<2>(J, batch, d_v, (long long)nv, d_last, d_mask, digits, st);
-    case 4: return launch_digits<4>(J, batch, d_v, (long long)nv, d_last, d_mask, digits, st);
-    case 7: return launch_digits<7>(J, batch, d_v, (long long)nv, d_last, d_mask, digits, st);
-    default: return launch_digits<14>(J, batch, d_v, (long long)nv, d_last, d_mask, digits, st);
-  }
+  return dispatch_limbs(J->p.field_limbs, [&](auto Lc) {
+    return launch_digits<Lc()>(J, batch, d_v, (long long)nv, d_last, d_mask, digits, st);
+  });
 }
 
 // 2. encode tails + MLWE finalize with their NTTs (prep256_kernel): jobs [0, n_enc) are the encode
@@ -2731,14 +2294,8 @@ static rg_status prep_launch(rg_jindo* J, size_t batch, size_t nv, const uint32_
   return check_launch("jindo prep");
 }
 
-// 2.-5. from the digits and the randomness: encode tails + MLWE finalize with their NTTs, then the core
-static rg_status commit_from_digits(rg_jindo* J, size_t batch, size_t nv, const uint32_t* digits, const int64_t* d_en,
-                                    const int64_t* d_mn, uint64_t* d_incom, uint64_t* d_enc, uint64_t* d_mlwe,
-                                    uint64_t* d_com, rg_jindo_scratch* sc, hipStream_t st) {
-  RG_TRY(prep_launch(J, batch, nv, digits, d_en, d_mn, d_enc, d_mlwe, kPrepAll, st));
-  return commit_core(J, batch, d_enc, d_mlwe, d_incom, d_com, sc, st);
-}
-
+// 1.-5.: the digits, then from them and the randomness the encode tails + MLWE finalize with their
+// NTTs, then the core
 static rg_status commit_dev(rg_jindo* J, size_t batch, const uint64_t* d_v, size_t nv, const uint64_t* d_last,
                             const uint64_t* d_mask, const int64_t* d_en, const int64_t* d_mn, uint64_t* d_incom,
                             uint64_t* d_enc, uint64_t* d_mlwe, uint64_t* d_com, hipStream_t st) {
@@ -2750,24 +2307,29 @@ static rg_status commit_dev(rg_jindo* J, size_t batch, const uint64_t* d_v, size
   RG_TRY(stream_scratch(J, batch, st, &sc));
   uint32_t* digits = sc->digits.as<uint32_t>();
   RG_TRY(digits_stage(J, batch, d_v, nv, d_last, d_mask, digits, st));
-  return commit_from_digits(J, batch, nv, digits, d_en, d_mn, d_incom, d_enc, d_mlwe, d_com, sc, st);
+  RG_TRY(prep_launch(J, batch, nv, digits, d_en, d_mn, d_enc, d_mlwe, kPrepAll, st));
+  return commit_core(J, batch, d_enc, d_mlwe, d_incom, d_com, sc, st);
 }
 
 // ---- sampling (csprng.hpp) -------------------------------------------------------------
+// a UniformSampler's key from its seed: SHA-384 -> AES-256 key schedule + big-endian IV
+static rg_status derive_key(const uint8_t* seed, size_t seed_len, AesKey& K) {
+  uint8_t r[48];
+  if (!sha384(seed, seed_len, r)) {
+    set_last_error("libcrypto SHA384 unavailable");
+    return RG_ERR_UNSUPPORTED;
+  }
+  aes256_expand(r, K.rk);
+  for (int w = 0; w < 4; ++w)
+    K.iv[w] = ((uint32_t)r[32 + 4 * w] << 24) | ((uint32_t)r[33 + 4 * w] << 16) | ((uint32_t)r[34 + 4 * w] << 8) |
+              r[35 + 4 * w];
+  return RG_OK;
+}
+
 static rg_status make_keys(const rg_jindo_seeds* seeds, AesKey* keys) {
   const uint8_t* sd[kNumDom] = {seeds->enc_cdt, seeds->enc_cosac, seeds->enc_cosac_round,
                                 seeds->mlwe_cdt, seeds->mlwe_round, seeds->uniform};
-  for (int i = 0; i < kNumDom; ++i) {
-    uint8_t r[48];
-    if (!sha384(sd[i], 32, r)) {
-      set_last_error("libcrypto SHA384 unavailable");
-      return RG_ERR_UNSUPPORTED;
-    }
-    aes256_expand(r, keys[i].rk);
-    for (int w = 0; w < 4; ++w)
-      keys[i].iv[w] = ((uint32_t)r[32 + 4 * w] << 24) | ((uint32_t)r[33 + 4 * w] << 16) | ((uint32_t)r[34 + 4 * w] << 8) |
-                      r[35 + 4 * w];
-  }
+  for (int i = 0; i < kNumDom; ++i) RG_TRY(derive_key(sd[i], 32, keys[i]));
   return RG_OK;
 }
 
@@ -2778,8 +2340,7 @@ static rg_status launch_uniform(const rg_jindo* J, size_t batch, const AesKey& k
   a.s = shape_of(J->p, 1);
   a.key = key;
   a.te0 = J->smp.te0.as<uint32_t>();
-  memcpy(a.F.q, J->field.q, 8 * L);
-  a.F.qinv = J->field.qinv;
+  a.F = field_params<L>(&J->field);
   // element.go:305-318: bitLen of q - 1, k bytes, top-byte mask
   int bitlen = 0;
   {
@@ -2849,7 +2410,6 @@ static rg_status sample_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, si
   SampleArgs a;
   memset(&a, 0, sizeof(a));
   RG_TRY(make_keys(seeds, a.key));
-  rg_status s;
   if (!sc->wq.p) {  // [0] cdt2's chunk counter, [2..3] cosac2's job counter, [4] uniform's long-draw flag
     std::lock_guard<std::mutex> lk(J->mu);
     RG_TRY(sc->wq.alloc(256));
@@ -2859,14 +2419,9 @@ static rg_status sample_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, si
     RG_HIP(hipEventRecord(e_start, st));
     RG_HIP(hipStreamWaitEvent(s_ml, e_start, 0));
   }
-  switch (p.field_limbs) {
-    case 1: s = launch_uniform<1>(J, batch, a.key[kDomUniform], first, d_last, d_mask, uflag, st); break;
-    case 2: s = launch_uniform<2>(J, batch, a.key[kDomUniform], first, d_last, d_mask, uflag, st); break;
-    case 4: s = launch_uniform<4>(J, batch, a.key[kDomUniform], first, d_last, d_mask, uflag, st); break;
-    case 7: s = launch_uniform<7>(J, batch, a.key[kDomUniform], first, d_last, d_mask, uflag, st); break;
-    default: s = launch_uniform<14>(J, batch, a.key[kDomUniform], first, d_last, d_mask, uflag, st); break;
-  }
-  RG_TRY(s);
+  RG_TRY(dispatch_limbs(p.field_limbs, [&](auto Lc) {
+    return launch_uniform<Lc()>(J, batch, a.key[kDomUniform], first, d_last, d_mask, uflag, st);
+  }));
   RG_TRY(digits_stage(J, batch, d_v, nv, d_last, d_mask, digits, st));
   a.s = shape_of(p, (long long)nv);
   a.te0 = S.te0.as<uint32_t>();
@@ -2945,14 +2500,10 @@ static rg_status sample_scratch(rg_jindo* J, size_t batch, rg_jindo_scratch* sc,
   return RG_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// Prover.Evaluate core (prover.go:205-324): the MulCoeffsMontgomeryThenAdd loops, with the
-// Fiat-Shamir challenges (batch, left, chals) injected by the caller.  Every loop is a
-// per-(limb, coeff) dot product, so each maps onto mac_kernel with J = 1 and the loop's own
-// strides.
-// ------------------------------------------------------------------------------------------
-static MacArgs dot_args(const RnsPrime* P, int nl, int d, long long nout, int T, const uint64_t* A, const uint64_t* B,
-                        long long b_out, long long b_term, uint64_t* out) {
+// MacArgs of a J = 1 dot product over T terms with the caller's strides (Prover.Evaluate's and the
+// verifier's loops); the commit's two products start from it and set J and their second operand set
+MacArgs dot_args(const RnsPrime* P, int nl, int d, long long nout, int T, const uint64_t* A, const uint64_t* B,
+                 long long b_out, long long b_term, uint64_t* out) {
   MacArgs m;
   memset(&m, 0, sizeof(m));
   m.d = d;
@@ -2969,446 +2520,21 @@ static MacArgs dot_args(const RnsPrime* P, int nl, int d, long long nout, int T,
   return m;
 }
 
-// Prover.Evaluate's batch combination (prover.go:254-266): a J = 1 dot product over the batch's
-// T commits, out[col][lk] = (sum_t A[t][lk] B[col][t][lk]) 2^-64 mod q, read once from HBM.
-// T = batch is the long axis (512 at the configs[4] shard) and the column count is modest (the
-// 144 InCommit / 432 MLWE polynomials), so mac_kernel's thread per (4 columns, lk) left too few
-// waves in flight for the opening stream.  Here a 256-thread workgroup owns 64 lk x NC columns
-// and its 4 waves split the terms (wave w: t = w, w + 4, ...), each term's loads unrolled x2;
-// the four exact 128-bit partial sums are added through LDS, then reduced once.
-constexpr int kDotNC = 4;
-__global__ __launch_bounds__(256) void dot_split_kernel(MacArgs a) {
-  __shared__ uint64_t red[3][kDotNC][2][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long long per_col = (long long)a.nl * a.d;
-  const long long nlkb = per_col / 64;
-  const long long lk = (blockIdx.x % nlkb) * 64 + lane;
-  const long long col0 = (blockIdx.x / nlkb) * kDotNC;
-  const int nc = (int)min((long long)kDotNC, a.ncols - col0);
-  const int T = a.T1;
-  Acc<false> acc[kDotNC];
-#pragma unroll
-  for (int c = 0; c < kDotNC; ++c) acc[c].zero();
-  const uint64_t* A = a.A1 + lk;
-  const uint64_t* Bp = a.B1 + lk;
-#pragma unroll 2
-  for (int t = w; t < T; t += 4) {
-    const uint64_t av = A[(long long)t * per_col];
-    uint64_t bv[kDotNC];
-#pragma unroll
-    for (int c = 0; c < kDotNC; ++c) bv[c] = c < nc ? Bp[(col0 + c) * a.b1_col + t * a.b1_term] : 0;
-#pragma unroll
-    for (int c = 0; c < kDotNC; ++c) acc[c].mac(av, bv[c]);
-  }
-  if (w > 0) {
-#pragma unroll
-    for (int c = 0; c < kDotNC; ++c) {
-      red[w - 1][c][0][lane] = acc[c].lo;
-      red[w - 1][c][1][lane] = acc[c].hi;
-    }
-  }
-  __syncthreads();
-  if (w != 0) return;
-  const RnsPrime& P = a.P[(int)(lk / a.d)];
-#pragma unroll
-  for (int c = 0; c < kDotNC; ++c) {
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {  // exact: (lo, hi) += (lo', hi'), the sum stays below 2^128
-      uint32_t cy = 0;
-      acc[c].lo = addc(acc[c].lo, red[v][c][0][lane], cy);
-      acc[c].hi += red[v][c][1][lane] + cy;
-    }
-    if (c < nc) a.out[(col0 + c) * per_col + lk] = acc[c].reduce(P);
-  }
-}
-
-static rg_status launch_dot(const MacArgs& m, hipStream_t st) {
-  uint64_t qmax = 0;
-  for (int l = 0; l < m.nl; ++l) qmax = std::max(qmax, m.P[l].q);
-  const bool narrow = 2.0 * log2((double)(qmax - 1)) + log2((double)m.T1 + 1.0) < 127.5;
-  if (m.J != 1 || m.T2 != 0 || m.C || !narrow || (m.nl * m.d) % 64 != 0)
-    return launch_mac(m, st);
-  const long long blocks = (m.ncols + kDotNC - 1) / kDotNC * ((long long)m.nl * m.d / 64);
-  hipLaunchKernelGGL(dot_split_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m);
-  return check_launch("jindo eval dot");
-}
-
-static rg_status eval_batch(const rg_jindo* J, size_t batch, const uint64_t* incom, const uint64_t* enc,
-                            const uint64_t* mlwe, const uint64_t* bq, const uint64_t* bo, uint64_t* ob_incom,
-                            uint64_t* ob_enc, uint64_t* ob_mlwe, hipStream_t st) {
-  const rg_jindo_params& p = J->p;
-  const long long pq = (long long)p.nq * p.d, po = (long long)p.nqo * p.d, nm = p.in_msis + p.mlwe;
-  const long long n_inc = p.dcmp, n_enc = (long long)(p.cols + 1) * p.rows, n_ml = (long long)(p.cols + 1) * nm;
-  if (!bq) {  // params.batch == 1: openBatch = open[0] (prover.go:267-269)
-    RG_HIP(hipMemcpyAsync(ob_incom, incom, 8 * n_inc * po, hipMemcpyDeviceToDevice, st));
-    RG_HIP(hipMemcpyAsync(ob_enc, enc, 8 * n_enc * pq, hipMemcpyDeviceToDevice, st));
-    RG_HIP(hipMemcpyAsync(ob_mlwe, mlwe, 8 * n_ml * pq, hipMemcpyDeviceToDevice, st));
-    return RG_OK;
-  }
-  const int T = (int)batch;  // term i = commit i, scaled by its batch challenge (:254-266)
-  RG_TRY(launch_dot(dot_args(J->ro, p.nqo, p.d, n_inc, T, bo, incom, po, n_inc * po, ob_incom), st));
-  RG_TRY(launch_dot(dot_args(J->rq, p.nq, p.d, n_enc, T, bq, enc, pq, n_enc * pq, ob_enc), st));
-  RG_TRY(launch_dot(dot_args(J->rq, p.nq, p.d, n_ml, T, bq, mlwe, pq, n_ml * pq, ob_mlwe), st));
-  return RG_OK;
-}
-
-// x mod q over limb-planar polynomials (Shoup by 1 reduces any 64-bit word): folds the
-// cross-GPU sum of partial openBatches (each < q, at most 2^64 / q of them) back to residues
-__global__ __launch_bounds__(256) void rns_reduce_kernel(uint64_t* x, long long npoly, int nl, int d, RingDev R) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npoly * nl * d) return;
-  const RnsPrime& P = R.p[(int)((i / d) % nl)];
-  x[i] = sh_mul(x[i], 1, P.one_sh, P.q);
-}
-
 }  // namespace rg
 
 using namespace rg;
 
-// ---- Verifier.Verify (verifier.go:50-282) ----------------------------------------------------
-// nmTest < nm with nmTest = Float64(isqrt(S)) (verifyNorm :278-281), decided exactly: the test is
-// S < K^2 with K the smallest integer whose float64 is >= nm (ceil(nm) up to 2^53; above, the
-// midpoint below nm, + 1 when nm's mantissa is odd, as ties round to even).
-static bool norm_below(const uint64_t* S, double nm) {
-  constexpr int NW = kNormW;
-  if (!(nm > 0)) return false;
-  uint64_t K[NW] = {0}, K2[2 * NW] = {0};
-  int e;
-  const double fr = frexp(nm, &e);
-  const uint64_t M = (uint64_t)ldexp(fr, 53);
-  const int E = e - 53;
-  if (E <= 0) {
-    const double c = ceil(nm);
-    if (c >= 18446744073709551616.0) return true;
-    K[0] = (uint64_t)c;
-  } else {
-    if (E / 64 >= NW) return true;
-    const int sub_e = (M == (1ull << 52)) ? E - 2 : E - 1;  // half the gap to the double below
-    K[E / 64] = M << (E % 64);
-    if (E % 64 && E / 64 + 1 < NW) K[E / 64 + 1] = M >> (64 - E % 64);
-    uint64_t h[NW] = {0};
-    if (sub_e >= 0) h[sub_e / 64] = 1ull << (sub_e % 64);
-    HostField::sub_n(K, K, h, NW);
-    if (M & 1)
-      for (int k = 0; k < NW; ++k)
-        if (++K[k]) break;
-  }
-  for (int a = 0; a < NW; ++a) {
-    uint64_t c = 0;
-    for (int b = 0; b < NW; ++b) {
-      const unsigned __int128 t = (unsigned __int128)K[a] * K[b] + K2[a + b] + c;
-      K2[a + b] = (uint64_t)t;
-      c = (uint64_t)(t >> 64);
-    }
-    K2[a + NW] += c;
-  }
-  for (int w = 2 * NW - 1; w >= NW; --w)
-    if (K2[w]) return true;
-  for (int w = NW - 1; w >= 0; --w)
-    if (S[w] != K2[w]) return S[w] < K2[w];
-  return false;
-}
-
-template <int L>
-static rg_status launch_decode(const rg_jindo* J, const uint64_t* in, long long npoly, int nout, uint64_t* out,
-                               hipStream_t st) {
-  if (npoly == 0) return RG_OK;
-  const rg_jindo_params& p = J->p;
-  DecodeArgs<L> a;
-  memset(&a, 0, sizeof(a));
-  a.d = p.d;
-  a.slots = p.slots;
-  a.exp = p.exp;
-  a.nout = nout;
-  a.R = ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b);
-  a.crt = J->crt_q;
-  memcpy(a.F.q, J->field.q, 8 * L);
-  a.F.qinv = J->field.qinv;
-  const HostField H(&J->field);
-  uint64_t t32[16], t64[16];
-  H.from_u64(t32, 1ull << 32);
-  H.mul(t64, t32, t32);  // Montgomery form of 2^64
-  memcpy(a.pw[0], J->field.r2, 8 * L);
-  for (int i = 1; i < 4; ++i) H.mul(a.pw[i], a.pw[i - 1], t64);
-  H.from_u64(a.bmont, p.base);
-  a.in = in;
-  a.out = out;
-  const size_t lds = ((size_t)p.nq * p.d + (size_t)p.d * L) * 8;
-  hipLaunchKernelGGL(decode_kernel<L>, dim3((unsigned)npoly), dim3(256), lds, st, a);
-  return check_launch("jindo decode");
-}
-
-template <int L>
-static rg_status launch_dot2(const rg_jindo* J, const uint64_t* x1, const uint64_t* y1, long long n1,
-                             const uint64_t* x2, const uint64_t* y2, long long n2, uint64_t* out, hipStream_t st) {
-  FieldParams<L> F;
-  memcpy(F.q, J->field.q, 8 * L);
-  F.qinv = J->field.qinv;
-  hipLaunchKernelGGL(dot2_kernel<L>, dim3(1), dim3(256), 0, st, F, x1, y1, n1, x2, y2, n2, out);
-  return check_launch("jindo dot");
-}
-
-static rg_status decode_any(const rg_jindo* J, const uint64_t* in, long long npoly, int nout, uint64_t* out,
-                            hipStream_t st) {
-  switch (J->p.field_limbs) {
-    case 1: return launch_decode<1>(J, in, npoly, nout, out, st);
-    case 2: return launch_decode<2>(J, in, npoly, nout, out, st);
-    case 4: return launch_decode<4>(J, in, npoly, nout, out, st);
-    case 7: return launch_decode<7>(J, in, npoly, nout, out, st);
-    default: return launch_decode<14>(J, in, npoly, nout, out, st);
-  }
-}
-static rg_status dot2_any(const rg_jindo* J, const uint64_t* x1, const uint64_t* y1, long long n1, const uint64_t* x2,
-                          const uint64_t* y2, long long n2, uint64_t* out, hipStream_t st) {
-  switch (J->p.field_limbs) {
-    case 1: return launch_dot2<1>(J, x1, y1, n1, x2, y2, n2, out, st);
-    case 2: return launch_dot2<2>(J, x1, y1, n1, x2, y2, n2, out, st);
-    case 4: return launch_dot2<4>(J, x1, y1, n1, x2, y2, n2, out, st);
-    case 7: return launch_dot2<7>(J, x1, y1, n1, x2, y2, n2, out, st);
-    default: return launch_dot2<14>(J, x1, y1, n1, x2, y2, n2, out, st);
-  }
-}
-
-static rg_status launch_norm(const rg_jindo* J, bool outer, const uint64_t* in, long long npoly, long long stride,
-                             uint64_t* out, hipStream_t st) {
-  if (npoly == 0) return RG_OK;
-  const rg_jindo_params& p = J->p;
-  NormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d = p.d;
-  a.R = outer ? ring_dev(J->ro, p.nqo, J->rootso_f, J->rootso_b) : ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b);
-  a.crt = outer ? J->crt_o : J->crt_q;
-  a.in = in;
-  a.in_stride = stride;
-  a.out = out;
-  const size_t lds = std::max((size_t)a.R.n * p.d, (size_t)256 * kNormW) * 8;
-  hipLaunchKernelGGL(norm_kernel, dim3((unsigned)npoly), dim3(256), lds, st, a);
-  return check_launch("jindo norm");
-}
-
-static rg_status launch_combine(const RnsPrime* P, int nl, int d, int cut, const uint64_t* A, const uint64_t* B,
-                                uint64_t* out, long long npoly, hipStream_t st) {
-  uint64_t c[4] = {0, 0, 0, 0};
-  RingDev R;
-  memset(&R, 0, sizeof(R));
-  R.n = nl;
-  for (int l = 0; l < nl; ++l) {
-    R.p[l] = P[l];
-    unsigned __int128 x = 1;
-    for (int i = 0; i < cut; ++i) x = (x * 2) % P[l].q;  // 2^cut mod q
-    c[l] = (uint64_t)x;
-  }
-  const long long n = npoly * nl * d;
-  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, B, out, n, nl, d, R, c[0],
-                     c[1], c[2], c[3]);
-  return check_launch("jindo combine");
-}
-
 extern "C" {
 
-rg_status rg_jindo_eval_batch_dev(const rg_jindo* J, size_t batch, const uint64_t* d_incom, const uint64_t* d_enc,
-                                  const uint64_t* d_mlwe, const uint64_t* d_bq, const uint64_t* d_bo,
-                                  uint64_t* d_ob_incom, uint64_t* d_ob_enc, uint64_t* d_ob_mlwe, void* stream) {
-  if (!J || batch == 0 || !d_incom || !d_enc || !d_mlwe || !d_ob_incom || !d_ob_enc || !d_ob_mlwe ||
-      (!d_bq != !d_bo) || (!d_bq && batch != 1))
-    return RG_ERR_INVALID;
-  return eval_batch(J, batch, d_incom, d_enc, d_mlwe, d_bq, d_bo, d_ob_incom, d_ob_enc, d_ob_mlwe, as_stream(stream));
-}
-
-rg_status rg_jindo_eval_partial_dev(const rg_jindo* J, const uint64_t* d_ob_enc, const uint64_t* d_left,
-                                    uint64_t* d_partial, void* stream) {
-  if (!J || !d_ob_enc || !d_left || !d_partial) return RG_ERR_INVALID;
-  const rg_jindo_params& p = J->p;
-  const long long pq = (long long)p.nq * p.d;
-  // out i in [0, cols]: sum_j left[j] * Enc[i][j] (prover.go:274-282); i = cols is PartialMask
-  return launch_mac(dot_args(J->rq, p.nq, p.d, p.cols + 1, p.rows, d_left, d_ob_enc, (long long)p.rows * pq, pq,
-                             d_partial),
-                    as_stream(stream));
-}
-
-rg_status rg_jindo_eval_respond_dev(const rg_jindo* J, const uint64_t* d_ob_enc, const uint64_t* d_ob_mlwe,
-                                    const uint64_t* d_chals, uint64_t* d_pf_enc, uint64_t* d_pf_mlwe, void* stream) {
-  if (!J || !d_ob_enc || !d_ob_mlwe || !d_chals || !d_pf_enc || !d_pf_mlwe) return RG_ERR_INVALID;
-  const rg_jindo_params& p = J->p;
-  const long long pq = (long long)p.nq * p.d, nm = p.in_msis + p.mlwe;
-  hipStream_t st = as_stream(stream);
-  // pf.Encode[i] = Enc[cols][i] + sum_j chals[j] * Enc[j][i] (prover.go:300-306)
-  MacArgs e = dot_args(J->rq, p.nq, p.d, p.rows, p.cols, d_chals, d_ob_enc, pq, (long long)p.rows * pq, d_pf_enc);
-  e.C = d_ob_enc + (long long)p.cols * p.rows * pq;
-  e.c_col = pq;
-  RG_TRY(launch_mac(e, st));
-  // pf.MLWE[i] = MLWE[cols][i] + sum_j chals[j] * MLWE[j][i] (:308-314)
-  MacArgs m = dot_args(J->rq, p.nq, p.d, nm, p.cols, d_chals, d_ob_mlwe, pq, nm * pq, d_pf_mlwe);
-  m.C = d_ob_mlwe + (long long)p.cols * nm * pq;
-  m.c_col = pq;
-  return launch_mac(m, st);
-}
-
-
-rg_status rg_jindo_verify_dev(const rg_jindo* J, size_t batch, const uint64_t* d_com, const uint64_t* d_bq,
-                              const uint64_t* d_bo, const uint64_t* d_chals, const uint64_t* d_left,
-                              const uint64_t* d_right, const uint64_t* d_y, const uint64_t* d_pf_incom,
-                              const uint64_t* d_pf_partial, const uint64_t* d_pf_enc, const uint64_t* d_pf_mlwe,
-                              double in_com_dcmp_two_nm, double res_two_nm, rg_jindo_verify_result* res,
-                              void* stream) {
-  if (!J || !res || !d_com || !d_chals || !d_left || !d_right || !d_y || !d_pf_incom || !d_pf_partial || !d_pf_enc ||
-      !d_pf_mlwe)
-    return RG_ERR_INVALID;
-  if (batch < 1 || (batch > 1 && (!d_bq || !d_bo))) return RG_ERR_INVALID;
-  RG_TRY(on_device(J));
-  const rg_jindo_params& p = J->p;
-  const int d = p.d, nq = p.nq, nqo = p.nqo, L = p.field_limbs;
-  const long long pq = (long long)nq * d, po = (long long)nqo * d, nm = p.in_msis + p.mlwe;
-  hipStream_t st = as_stream(stream);
-  const long long n_out = p.dcmp + p.out_msis, n_in = p.rows + nm + p.in_msis;
-  DevBuf a_out, b_out, c_out, lift, a_in, b_in, c_in, p1, p2, norms, flag, dcd, bd, ev;
-  RG_TRY(a_out.alloc(8 * p.out_msis * po));
-  RG_TRY(b_out.alloc(8 * p.out_msis * po));
-  RG_TRY(c_out.alloc(8 * p.out_msis * po));
-  RG_TRY(lift.alloc(8 * p.dcmp * pq));
-  RG_TRY(a_in.alloc(8 * p.in_msis * pq));
-  RG_TRY(b_in.alloc(8 * p.in_msis * pq));
-  RG_TRY(c_in.alloc(8 * p.in_msis * pq));
-  RG_TRY(p1.alloc(8 * pq));
-  RG_TRY(p2.alloc(8 * pq));
-  RG_TRY(norms.alloc(8 * (n_out + n_in) * kNormW));
-  RG_TRY(flag.alloc(sizeof(int)));
-  RG_TRY(dcd.alloc(8 * (size_t)p.cols * p.slots * L));
-  RG_TRY(bd.alloc(8 * (size_t)batch * L));
-  RG_TRY(ev.alloc(8 * 2 * (size_t)L));
-  uint64_t* nrm = norms.as<uint64_t>();
-  // verifyOuterCommitment (:136-161): A = sum_j com[j][i] * batchOut[j] (or com[0][i]),
-  // C = A * 2^logOutCut - sum_j Out[i][j] * Proof.InCommit[j]
-  if (batch > 1) {
-    MacArgs m = dot_args(J->ro, nqo, d, p.out_msis, (int)batch, d_bo, d_com, pq, (long long)p.out_msis * pq,
-                         a_out.as<uint64_t>());
-    RG_TRY(launch_mac(m, st));
-  } else {
-    RG_HIP(hipMemcpy2DAsync(a_out.p, 8 * po, d_com, 8 * pq, 8 * po, p.out_msis, hipMemcpyDeviceToDevice, st));
-  }
-  {
-    MacArgs m = dot_args(J->ro, nqo, d, 1, p.dcmp, J->ck_out.as<uint64_t>(), d_pf_incom, 0, po, b_out.as<uint64_t>());
-    m.J = p.out_msis;
-    RG_TRY(launch_mac(m, st));
-  }
-  RG_TRY(launch_combine(J->ro, nqo, d, p.log_out_cut, a_out.as<uint64_t>(), b_out.as<uint64_t>(), c_out.as<uint64_t>(),
-                        p.out_msis, st));
-  RG_TRY(launch_norm(J, true, d_pf_incom, p.dcmp, po, nrm, st));
-  RG_TRY(launch_norm(J, true, c_out.as<uint64_t>(), p.out_msis, po, nrm + p.dcmp * kNormW, st));
-  // verifyInnerCommitment (:164-200): lift = MForm(NTT(ModUpQtoP(pfInv.InCommit))) (centred),
-  // A = sum_{j<cols} lift[j in_msis + i] * chals[j] + lift[cols in_msis + i],
-  // C = A * 2^logInCut - (sum In[i][j] * Encode[j] + sum MLWE_ck[i][j] * MLWE[j] + MLWE[mlwe + i])
-  {
-    RoundArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.d = d;
-    ra.cut = 0;
-    ra.src = ring_dev(J->ro, nqo, J->rootso_f, J->rootso_b);
-    ra.dst = ring_dev(J->rq, nq, J->rootsq_f, J->rootsq_b);
-    ra.crt = J->crt_o;
-    ra.dm = J->dst_q;
-    ra.in = d_pf_incom;
-    ra.out = lift.as<uint64_t>();
-    ra.out_stride = pq;
-    ra.out_rows = nq;
-    RG_TRY(launch_round(ra, p.dcmp, st));
-  }
-  {
-    MacArgs m = dot_args(J->rq, nq, d, p.in_msis, p.cols, d_chals, lift.as<uint64_t>(), pq, (long long)p.in_msis * pq,
-                         a_in.as<uint64_t>());
-    m.C = lift.as<uint64_t>() + (long long)p.cols * p.in_msis * pq;
-    m.c_col = pq;
-    RG_TRY(launch_mac(m, st));
-  }
-  {
-    MacArgs m = dot_args(J->rq, nq, d, 1, p.rows, J->ck_in.as<uint64_t>(), d_pf_enc, 0, pq, b_in.as<uint64_t>());
-    m.J = p.in_msis;
-    m.T2 = p.mlwe;
-    m.A2 = J->ck_mlwe.as<uint64_t>();
-    m.B2 = d_pf_mlwe;
-    m.b2_term = pq;
-    m.C = d_pf_mlwe + (long long)p.mlwe * pq;
-    m.c_j = pq;
-    RG_TRY(launch_mac(m, st));
-  }
-  RG_TRY(launch_combine(J->rq, nq, d, p.log_in_cut, a_in.as<uint64_t>(), b_in.as<uint64_t>(), c_in.as<uint64_t>(),
-                        p.in_msis, st));
-  uint64_t* nin = nrm + n_out * kNormW;
-  RG_TRY(launch_norm(J, false, d_pf_enc, p.rows, pq, nin, st));
-  RG_TRY(launch_norm(J, false, d_pf_mlwe, nm, pq, nin + p.rows * kNormW, st));
-  RG_TRY(launch_norm(J, false, c_in.as<uint64_t>(), p.in_msis, pq, nin + (p.rows + nm) * kNormW, st));
-  // verifyConsistency (:203-221): sum left[i] * Encode[i] == sum chals[i] * Partial[i] + PartialMask
-  RG_TRY(launch_mac(dot_args(J->rq, nq, d, 1, p.rows, d_left, d_pf_enc, 0, pq, p1.as<uint64_t>()), st));
-  {
-    MacArgs m = dot_args(J->rq, nq, d, 1, p.cols, d_chals, d_pf_partial, 0, pq, p2.as<uint64_t>());
-    m.C = d_pf_partial + (long long)p.cols * pq;
-    RG_TRY(launch_mac(m, st));
-  }
-  RG_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  hipLaunchKernelGGL(neq_kernel, dim3((unsigned)((pq + 255) / 256)), dim3(256), 0, st, p1.as<uint64_t>(),
-                     p2.as<uint64_t>(), pq, flag.as<int>());
-  RG_TRY(check_launch("jindo consistency"));
-  // verifyEval (:224-259): sum_{i,j} right[i slots + j] * Decode(pfInv.Partial[i])[j] ==
-  // sum_i Decode(INTT(IMForm(batch[i])))[0] * y[i]  (or y[0])
-  RG_TRY(decode_any(J, d_pf_partial, p.cols, p.slots, dcd.as<uint64_t>(), st));
-  const uint64_t* yb = d_y;
-  if (batch > 1) {
-    RG_TRY(decode_any(J, d_bq, (long long)batch, 1, bd.as<uint64_t>(), st));
-    yb = bd.as<uint64_t>();
-  }
-  RG_TRY(dot2_any(J, d_right, dcd.as<uint64_t>(), (long long)p.cols * p.slots, yb, d_y, batch > 1 ? (long long)batch : 0,
-                  ev.as<uint64_t>(), st));
-  // results to the host
-  std::vector<uint64_t> hn((size_t)(n_out + n_in) * kNormW), he(2 * L);
-  int hf = 0;
-  RG_HIP(hipMemcpyAsync(hn.data(), nrm, hn.size() * 8, hipMemcpyDeviceToHost, st));
-  RG_HIP(hipMemcpyAsync(he.data(), ev.p, he.size() * 8, hipMemcpyDeviceToHost, st));
-  RG_HIP(hipMemcpyAsync(&hf, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  RG_HIP(hipStreamSynchronize(st));
-  memset(res, 0, sizeof(*res));
-  for (long long i = 0; i < n_out; ++i) {
-    uint32_t c = 0;
-    for (int w = 0; w < kNormW; ++w) {
-      const unsigned __int128 t = (unsigned __int128)res->outer_norm_sq[w] + hn[i * kNormW + w] + c;
-      res->outer_norm_sq[w] = (uint64_t)t;
-      c = (uint32_t)(t >> 64);
-    }
-  }
-  for (long long i = n_out; i < n_out + n_in; ++i) {
-    uint32_t c = 0;
-    for (int w = 0; w < kNormW; ++w) {
-      const unsigned __int128 t = (unsigned __int128)res->inner_norm_sq[w] + hn[i * kNormW + w] + c;
-      res->inner_norm_sq[w] = (uint64_t)t;
-      c = (uint32_t)(t >> 64);
-    }
-  }
-  res->outer_ok = norm_below(res->outer_norm_sq, in_com_dcmp_two_nm);
-  res->inner_ok = norm_below(res->inner_norm_sq, res_two_nm);
-  res->consistency_ok = hf == 0;
-  memcpy(res->eval_lhs, he.data(), 8 * L);
-  if (batch > 1) {
-    memcpy(res->eval_rhs, he.data() + L, 8 * L);
-  } else {
-    RG_HIP(hipMemcpy(res->eval_rhs, d_y, 8 * L, hipMemcpyDeviceToHost));
-  }
-  res->eval_ok = memcmp(res->eval_lhs, res->eval_rhs, 8 * L) == 0;
-  res->ok = res->outer_ok && res->inner_ok && res->consistency_ok && res->eval_ok;
-  return RG_OK;
-}
-
-static rg_status jindo_new(const rg_jindo_params* p, rg_jindo** out, rg_jindo** J) {
+// A validated handle with its ring tables, owned by the caller until it hands it out
+static rg_status jindo_new(const rg_jindo_params* p, rg_jindo** out, std::unique_ptr<rg_jindo>& J) {
   if (!out) return RG_ERR_INVALID;
   *out = nullptr;
   RG_TRY(validate(p));
-  *J = new rg_jindo();
-  (*J)->p = *p;
-  if (hipGetDevice(&(*J)->device) != hipSuccess) (*J)->device = 0;
-  rg_status s = build(*J);
-  if (s != RG_OK) {
-    delete *J;
-    *J = nullptr;
-  }
-  return s;
+  J.reset(new rg_jindo());
+  J->p = *p;
+  if (hipGetDevice(&J->device) != hipSuccess) J->device = 0;
+  return build(J.get());
 }
 
 // The commit key is device-resident from here on: ck_in/ck_mlwe/ck_out hold it in the
@@ -3457,39 +2583,30 @@ static rg_status take_ck(rg_jindo* J, const uint64_t* ck_in, const uint64_t* ck_
 rg_status rg_jindo_create(const rg_jindo_params* p, const uint64_t* ck_in, const uint64_t* ck_mlwe,
                           const uint64_t* ck_out, rg_jindo** out) {
   if (!ck_in || !ck_out || (!ck_mlwe && p && p->mlwe)) return RG_ERR_INVALID;
-  rg_jindo* J = nullptr;
-  RG_TRY(jindo_new(p, out, &J));
-  rg_status s = take_ck(J, ck_in, ck_mlwe, ck_out, hipMemcpyHostToDevice, nullptr);
-  if (s != RG_OK) {
-    delete J;
-    return s;
-  }
-  *out = J;
+  std::unique_ptr<rg_jindo> J;
+  RG_TRY(jindo_new(p, out, J));
+  RG_TRY(take_ck(J.get(), ck_in, ck_mlwe, ck_out, hipMemcpyHostToDevice, nullptr));
+  *out = J.release();
   return RG_OK;
 }
 
 rg_status rg_jindo_create_dev(const rg_jindo_params* p, const uint64_t* d_ck_in, const uint64_t* d_ck_mlwe,
                               const uint64_t* d_ck_out, void* stream, rg_jindo** out) {
   if (!d_ck_in || !d_ck_out || (!d_ck_mlwe && p && p->mlwe)) return RG_ERR_INVALID;
-  rg_jindo* J = nullptr;
-  RG_TRY(jindo_new(p, out, &J));
-  rg_status s = take_ck(J, d_ck_in, d_ck_mlwe, d_ck_out, hipMemcpyDeviceToDevice, as_stream(stream));
-  if (s != RG_OK) {
-    delete J;
-    return s;
-  }
-  *out = J;
+  std::unique_ptr<rg_jindo> J;
+  RG_TRY(jindo_new(p, out, J));
+  RG_TRY(take_ck(J.get(), d_ck_in, d_ck_mlwe, d_ck_out, hipMemcpyDeviceToDevice, as_stream(stream)));
+  *out = J.release();
   return RG_OK;
 }
 
 rg_status rg_jindo_create_from_crs(const rg_jindo_params* p, const uint8_t* crs, size_t crs_len, rg_jindo** out) {
   if (!crs && crs_len) return RG_ERR_INVALID;
-  rg_jindo* J = nullptr;
-  RG_TRY(jindo_new(p, out, &J));
+  std::unique_ptr<rg_jindo> J;
+  RG_TRY(jindo_new(p, out, J));
   const rg_jindo_params& P = J->p;
   CtrStream u(crs, crs_len);
   if (!u.ok) {
-    delete J;
     set_last_error("libcrypto (SHA384/AES-256-CTR) unavailable");
     return RG_ERR_UNSUPPORTED;
   }
@@ -3510,12 +2627,8 @@ rg_status rg_jindo_create_from_crs(const rg_jindo_params* p, const uint8_t* crs,
     for (int j = 0; j < P.dcmp; ++j)
       for (size_t k = 0; k < d; ++k)
         for (int l = 0; l < P.nqo; ++l) h_out[(((size_t)i * P.dcmp + j) * P.nqo + l) * d + k] = u.sample_n(P.qo[l]);
-  rg_status s = take_ck(J, h_in.data(), h_ml.data(), h_out.data(), hipMemcpyHostToDevice, nullptr);
-  if (s != RG_OK) {
-    delete J;
-    return s;
-  }
-  *out = J;
+  RG_TRY(take_ck(J.get(), h_in.data(), h_ml.data(), h_out.data(), hipMemcpyHostToDevice, nullptr));
+  *out = J.release();
   return RG_OK;
 }
 
@@ -3846,16 +2959,8 @@ rg_status rg_uniform_words_dev(const uint8_t* seed, size_t seed_len, unsigned lo
                                unsigned long long first_word, size_t n, uint64_t* d_out, void* stream) {
   if ((!seed && seed_len) || (!d_out && n)) return RG_ERR_INVALID;
   if (n == 0) return RG_OK;
-  uint8_t r[48];
-  if (!sha384(seed, seed_len, r)) {
-    set_last_error("libcrypto SHA384 unavailable");
-    return RG_ERR_UNSUPPORTED;
-  }
   AesKey K;
-  aes256_expand(r, K.rk);
-  for (int w = 0; w < 4; ++w)
-    K.iv[w] = ((uint32_t)r[32 + 4 * w] << 24) | ((uint32_t)r[33 + 4 * w] << 16) | ((uint32_t)r[34 + 4 * w] << 8) |
-              r[35 + 4 * w];
+  RG_TRY(derive_key(seed, seed_len, K));
   uint32_t te0[256];
   aes_te0(te0);
   DevBuf t;
@@ -3866,23 +2971,6 @@ rg_status rg_uniform_words_dev(const uint8_t* seed, size_t seed_len, unsigned lo
   RG_TRY(check_launch("uniform words"));
   RG_HIP(hipStreamSynchronize(st));  // `t` is freed on return
   return RG_OK;
-}
-
-rg_status rg_jindo_eval_reduce_dev(const rg_jindo* J, uint64_t* d_ob_incom, uint64_t* d_ob_enc, uint64_t* d_ob_mlwe,
-                                   void* stream) {
-  if (!J || !d_ob_incom || !d_ob_enc || !d_ob_mlwe) return RG_ERR_INVALID;
-  const rg_jindo_params& p = J->p;
-  hipStream_t st = as_stream(stream);
-  const long long nm = p.in_msis + p.mlwe, n_enc = (long long)(p.cols + 1) * p.rows, n_ml = (long long)(p.cols + 1) * nm;
-  const RingDev rq = ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b), ro = ring_dev(J->ro, p.nqo, J->rootso_f, J->rootso_b);
-  auto go = [&](uint64_t* x, long long npoly, int nl, const RingDev& R) {
-    const long long n = npoly * nl * p.d;
-    hipLaunchKernelGGL(rns_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, npoly, nl, p.d, R);
-    return check_launch("jindo eval reduce");
-  };
-  RG_TRY(go(d_ob_incom, p.dcmp, p.nqo, ro));
-  RG_TRY(go(d_ob_enc, n_enc, p.nq, rq));
-  return go(d_ob_mlwe, n_ml, p.nq, rq);
 }
 
 }  // extern "C"

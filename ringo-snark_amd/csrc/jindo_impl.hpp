@@ -1,0 +1,270 @@
+// jindo_impl.hpp -- what jindo.hip and jindo_verify.hip share: the device-side ring constants and
+// kernel argument structs, the __device__ helpers that kernels of both units inline (there is no
+// relocatable device code, so a kernel never calls across units), the handle, and the host
+// functions that cross units.  The pipeline overview is at the top of jindo.hip.
+#pragma once
+#include <map>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "common.hpp"
+#include "field.hpp"
+
+namespace rg {
+
+constexpr int kMaxQ = 4;     // RNS limbs per ring
+constexpr int kMaxD = 1024;  // ring degree supported by the LDS kernels
+constexpr int kMaxJ = 32;    // MSIS rank accumulated per thread
+
+struct RnsPrime {
+  uint64_t q;
+  uint64_t rinv, rinv_sh;    // 2^-64 mod q (IMForm)
+  uint64_t r64, r64_sh;      // 2^64 mod q (MForm)
+  uint64_t one_sh;           // floor(2^64 / q): x mod q = shoup(x, 1)
+  uint64_t ninv, ninv_sh;    // d^-1 mod q
+  uint64_t bmod, bmod_sh;    // base mod q
+  uint64_t rw1, rw1_sh;      // 2^64 w1 mod q, w1 = the forward table's first-stage root (prep256 stage 0)
+};
+
+struct RingDev {
+  int n;                    // limbs
+  RnsPrime p[kMaxQ];
+  const ulonglong2* fwd;    // [n][d] (w, w') psi^brv
+  const ulonglong2* bwd;    // [n][d] psi^-brv
+};
+
+// CRT (Garner) constants for a source ring
+struct CrtDev {
+  int n;
+  uint64_t q[kMaxQ];
+  uint64_t inv[kMaxQ][kMaxQ], inv_sh[kMaxQ][kMaxQ];  // inv[j][k] = q_k^-1 mod q_j (k < j)
+  uint64_t Q[4], Qhalf[4];                            // product (4 words) and floor(Q/2)
+};
+
+// destination mod constants: 2^(64k) mod q' for multiword reduction
+struct DstDev {
+  int n;
+  uint64_t pw[kMaxQ][4], pw_sh[kMaxQ][4];
+};
+
+// ------------------------------------------------------------------------------------------
+// device helpers
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t sh_mul(uint64_t y, uint64_t w, uint64_t wp, uint64_t q) {
+  return shoup_mul(y, w, wp, q);
+}
+
+// d-point inverse negacyclic NTT (GS, bit-reversed -> natural), times d^-1, of one limb held in
+// LDS, by `nt` threads (thread index `ti`); synchronises the whole workgroup between stages
+__device__ inline void intt_lds(uint64_t* p, int d, const ulonglong2* roots, const RnsPrime& P, int ti, int nt,
+                                bool active) {
+  const uint64_t q = P.q;
+  for (int m = d >> 1, t = 1, lt = 0; m >= 1; m >>= 1, t <<= 1, ++lt) {
+    if (active) {
+      for (int k = ti; k < (d >> 1); k += nt) {
+        const int i = k >> lt, j = (i << (lt + 1)) + (k & (t - 1));
+        const ulonglong2 w = roots[m + i];
+        const uint64_t u = p[j], v = p[j + t];
+        p[j] = mod_add(u, v, q);
+        p[j + t] = sh_mul(mod_sub(u, v, q), w.x, w.y, q);
+      }
+    }
+    __syncthreads();
+  }
+  if (active)
+    for (int k = ti; k < d; k += nt) p[k] = sh_mul(p[k], P.ninv, P.ninv_sh, q);
+  __syncthreads();
+}
+
+struct MacArgs {
+  int d, nl, J;            // degree, limbs, outputs per column
+  long long ncols;         // B * columns
+  int T1, T2;              // terms from operand set 1 / 2
+  const uint64_t* A1;      // [J][T1][nl][d]   commit key
+  const uint64_t* B1;      // [ncols][T1][nl][d] (stride b1_col per column, b1_term per term)
+  long long b1_col, b1_term;
+  const uint64_t* A2;      // [J][T2][nl][d]
+  const uint64_t* B2;
+  long long b2_col, b2_term;
+  const uint64_t* C;       // added after reduction: [ncols][...] + j * c_j  (nullable)
+  long long c_col, c_j;
+  uint64_t* out;           // [ncols][J][nl][d]
+  RnsPrime P[kMaxQ];
+};
+
+// acc += a * b as an exact multiword sum; WIDE keeps a third word (needed only when
+// (q-1)^2 * terms could reach 2^128: decided per launch on the host).
+template <bool WIDE>
+struct Acc {
+  uint64_t lo, hi;
+  uint32_t top;
+  __device__ __forceinline__ void zero() {
+    lo = hi = 0;
+    top = 0;
+  }
+  __device__ __forceinline__ void mac(uint64_t a, uint64_t b) {
+    uint64_t pl, ph;
+    mul_wide(a, b, pl, ph);
+    uint32_t c = 0;
+    lo = addc(lo, pl, c);
+    if constexpr (WIDE) {
+      uint32_t c2 = 0;
+      hi = addc(hi, ph, c2);
+      uint32_t c3 = 0;
+      hi = addc(hi, (uint64_t)c, c3);
+      top += c2 + c3;
+    } else {
+      hi += ph + c;
+    }
+  }
+  // (lo + hi 2^64 + top 2^128) * 2^-64 mod q = lo 2^-64 + hi + top 2^64
+  __device__ __forceinline__ uint64_t reduce(const RnsPrime& P) const {
+    const uint64_t q = P.q;
+    uint64_t r = sh_mul(lo, P.rinv, P.rinv_sh, q);
+    r = mod_add(r, sh_mul(hi, 1, P.one_sh, q), q);
+    if constexpr (WIDE) r = mod_add(r, sh_mul((uint64_t)top, P.r64, P.r64_sh, q), q);
+    return r;
+  }
+};
+
+struct RoundArgs {
+  int d, cut;
+  RingDev src, dst;
+  CrtDev crt;
+  DstDev dm;
+  const uint64_t* in;  // [npoly][src.n][d]
+  uint64_t* out;       // [npoly] at stride out_stride, dst.n limbs (+ zero rows up to out_rows)
+  long long out_stride;
+  int out_rows;
+  long long npoly;     // round256_kernel's polynomials (round_kernel: the grid)
+};
+
+__device__ __forceinline__ void mw_muladd(uint64_t* v, int nw, uint64_t m, uint64_t add) {
+  uint64_t carry = add;
+  for (int i = 0; i < nw; ++i) {
+    uint64_t lo, hi;
+    mul_wide(v[i], m, lo, hi);
+    uint32_t c = 0;
+    lo = addc(lo, carry, c);
+    v[i] = lo;
+    carry = hi + c;
+  }
+}
+
+// reconstructTo (rns.go:76-105) of one coefficient's residues r[ns] (coefficient domain): the
+// centred value as sign (returned) and 4-word magnitude
+__device__ __forceinline__ bool crt_centred(const CrtDev& crt, int ns, const uint64_t* r, uint64_t mag[4]) {
+  bool neg;
+  mag[0] = mag[1] = mag[2] = mag[3] = 0;
+  if (ns == 1) {  // reconstructTo fast path: toBalanced (rns.go:68-73,78-91)
+    const uint64_t q = crt.q[0];
+    neg = r[0] > (q >> 1);
+    mag[0] = neg ? q - r[0] : r[0];
+  } else {  // Garner: V = x0 + q0 (x1 + q1 (x2 + ...)) in [0, Q)  (rns.go:93-99)
+    uint64_t x[kMaxQ];
+    for (int j = 0; j < ns; ++j) {
+      const uint64_t qj = crt.q[j];
+      uint64_t v = r[j];
+      for (int kk = 0; kk < j; ++kk) {
+        uint64_t xk = x[kk];
+        // x_k < q_k must be below q_j for mod_sub: one subtraction where q_k < 2 q_j (primes of
+        // one bit size, every NewParameters ring), x_k % q_j for any other pair of primes
+        if (xk >= qj) xk = (xk - qj >= qj) ? xk % qj : xk - qj;
+        v = mod_sub(v, xk, qj);
+        v = sh_mul(v, crt.inv[j][kk], crt.inv_sh[j][kk], qj);
+      }
+      x[j] = v;
+    }
+    uint64_t V[4] = {x[ns - 1], 0, 0, 0};
+    for (int j = ns - 2; j >= 0; --j) mw_muladd(V, 4, crt.q[j], x[j]);
+    // V >= floor(Q/2) -> V - Q (rns.go:100-102)
+    bool ge = true;
+    for (int i = 3; i >= 0; --i) {
+      if (V[i] != crt.Qhalf[i]) {
+        ge = V[i] > crt.Qhalf[i];
+        break;
+      }
+    }
+    neg = ge;
+    if (neg) {
+      uint32_t br = 0;
+      for (int i = 0; i < 4; ++i) mag[i] = subb(crt.Q[i], V[i], br);
+    } else {
+      for (int i = 0; i < 4; ++i) mag[i] = V[i];
+    }
+  }
+  return neg;
+}
+
+}  // namespace rg
+
+// ------------------------------------------------------------------------------------------
+// the handle
+// ------------------------------------------------------------------------------------------
+// Scratch of one commit stream: digits [B][cols+1][rows][d] u32, inner commitments
+// [B][cols+1][inMSIS][nq][d], outer [B][outMSIS][nqo][d].  One per stream, so calls on
+// different streams never share scratch (calls on one stream are ordered by the stream).
+struct rg_jindo_scratch {
+  rg::DevBuf digits, com, ocom;
+  rg::DevBuf last, mask, en, mn;  // the sampled randomness of rg_jindo_commit_sampled_dev
+  rg::DevBuf wq;                  // cdt2_noise_kernel's chunk counter
+};
+
+// Sampler setup (rg_jindo_set_stddevs): the reference's six standard deviations and the tables
+// derived from them on the host (csprng_host.hpp)
+struct rg_jindo_samplers {
+  bool ready = false;
+  double sd[6];  // ecd, ecd_blind, mask, mask_blind, mlwe, mask_mlwe
+  rg::DevBuf te0, cdt_enc, cdt_guide, cdt_sbound, cdt_jmax, cdt_mlwe, zig, delta;
+  int cdt_enc_size = 0, cdt_mlwe_size = 0;
+  int64_t tail_lo_enc = 0, tail_lo_mlwe = 0;
+  std::vector<double> h_delta;
+};
+
+struct rg_jindo {
+  rg_jindo_params p;
+  rg_field field;
+  int device = 0;  // the handle's buffers live on this device
+  rg::RnsPrime rq[rg::kMaxQ], ro[rg::kMaxQ];
+  rg::DevBuf rootsq_f, rootsq_b, rootso_f, rootso_b;
+  rg::CrtDev crt_q, crt_o;
+  rg::DstDev dst_o, dst_q;
+  rg::DevBuf ck_in, ck_mlwe, ck_out;  // the commit key, device-resident (entities.go:21-73 layouts)
+  rg::DevBuf ckm_in, ckm_out;  // the same as base-256 digits for mac_mfma (inner, outer)
+  int mfma_q = 0, mfma_o = 0;  // digits per residue of the MFMA MAC (0: mac_kernel)
+  uint64_t base_inv;
+  std::mutex mu;  // guards `scratch` and `aux`
+  std::map<hipStream_t, std::unique_ptr<rg_jindo_scratch>> scratch;
+  rg_jindo_samplers smp;
+  // the sampled commit's helper streams and events, one set per caller stream (lazily created):
+  // s[0] runs the COSAC centres + cosac2, s[1] the MLWE samplers and their prep (commit_sampled_dev)
+  struct Aux {
+    hipStream_t s[2] = {nullptr, nullptr};
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  };
+  std::map<hipStream_t, Aux> aux;
+  ~rg_jindo() {
+    for (auto& kv : aux) {
+      for (hipStream_t x : kv.second.s)
+        if (x) (void)hipStreamDestroy(x);
+      for (hipEvent_t x : kv.second.e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  }
+};
+
+namespace rg {
+
+// jindo.hip
+RingDev ring_dev(const RnsPrime* P, int n, const DevBuf& f, const DevBuf& b);
+rg_status on_device(const rg_jindo* J);
+rg_status launch_mac(const MacArgs& m, hipStream_t st);
+// a CRT rounding from ring Q_out (src_o) or Q into Q_out (dst_o) or Q
+RoundArgs round_args(const rg_jindo* J, bool src_o, bool dst_o, int cut, const uint64_t* in, uint64_t* out,
+                     long long out_stride, int out_rows);
+rg_status launch_round(RoundArgs ra, long long npoly, hipStream_t st);
+MacArgs dot_args(const RnsPrime* P, int nl, int d, long long nout, int T, const uint64_t* A, const uint64_t* B,
+                 long long b_out, long long b_term, uint64_t* out);
+
+}  // namespace rg

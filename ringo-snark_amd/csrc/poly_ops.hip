@@ -150,8 +150,7 @@ template <int L>
 static PolyArgs<L> args_of(const rg_field* f) {
   PolyArgs<L> a;
   memset(&a, 0, sizeof(a));
-  memcpy(a.F.q, f->q, 8 * L);
-  a.F.qinv = f->qinv;
+  a.F = field_params<L>(f);
   return a;
 }
 
@@ -420,8 +419,7 @@ static rg_status modswitch_L(const rg_field* f, const uint64_t* pbig, int w, con
                              long long n, hipStream_t st) {
   MsArgs<L> a;
   memset(&a, 0, sizeof(a));
-  memcpy(a.F.q, f->q, 8 * L);
-  a.F.qinv = f->qinv;
+  a.F = field_params<L>(f);
   memcpy(a.r2, f->r2, 8 * L);
   a.in = pbig;
   a.out = out;
@@ -454,16 +452,6 @@ static rg_status modswitch_L(const rg_field* f, const uint64_t* pbig, int w, con
   return check_launch("modswitch");
 }
 
-#define RG_DISPATCH_L(L_, CALL)                 \
-  switch (L_) {                                 \
-    case 1: return CALL(1);                     \
-    case 2: return CALL(2);                     \
-    case 4: return CALL(4);                     \
-    case 7: return CALL(7);                     \
-    case 14: return CALL(14);                   \
-    default: return RG_ERR_UNSUPPORTED;         \
-  }
-
 static bool pow2(long long n) { return n > 0 && !(n & (n - 1)); }
 
 }  // namespace rg
@@ -483,9 +471,9 @@ rg_status rg_poly_quorem_vanishing_dev(const rg_field* f, size_t rank, long long
     return RG_OK;
   }
   if (d_quo == d_p) return RG_ERR_INVALID;  // rem may alias p (each lane reads its class first)
-#define RG_QR(L) quorem_L<L>(f, (long long)rank, n_vanish, d_quo, d_rem, d_p, (long long)batch, st)
-  RG_DISPATCH_L(f->L, RG_QR)
-#undef RG_QR
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    return quorem_L<Lc()>(f, (long long)rank, n_vanish, d_quo, d_rem, d_p, (long long)batch, st);
+  });
 }
 
 rg_status rg_poly_aut_dev(const rg_field* f, size_t rank, long long idx, int ntt_domain, uint64_t* d_out,
@@ -498,9 +486,9 @@ rg_status rg_poly_aut_dev(const rg_field* f, size_t rank, long long idx, int ntt
   long long k = idx % n2;  // cyclotomic.go:38-41
   if (k < 0) k += n2;
   hipStream_t st = as_stream(stream);
-#define RG_AUT(L) aut_L<L>(f, (long long)rank, k, ntt_domain != 0, d_out, d_p, (long long)batch, st)
-  RG_DISPATCH_L(f->L, RG_AUT)
-#undef RG_AUT
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    return aut_L<Lc()>(f, (long long)rank, k, ntt_domain != 0, d_out, d_p, (long long)batch, st);
+  });
 }
 
 rg_status rg_poly_evaluate_dev(const rg_field* f, const uint64_t* d_p, size_t n, const uint64_t* d_x, uint64_t* d_out,
@@ -511,9 +499,7 @@ rg_status rg_poly_evaluate_dev(const rg_field* f, const uint64_t* d_p, size_t n,
     RG_HIP(hipMemsetAsync(d_out, 0, f->L * 8, st));
     return RG_OK;
   }
-#define RG_EV(L) eval_L<L>(f, d_p, (long long)n, d_x, d_out, d_scratch, st)
-  RG_DISPATCH_L(f->L, RG_EV)
-#undef RG_EV
+  return dispatch_limbs(f->L, [&](auto Lc) { return eval_L<Lc()>(f, d_p, (long long)n, d_x, d_out, d_scratch, st); });
 }
 
 rg_status rg_poly_modswitch_dev(const rg_field* f, size_t n, const uint64_t* d_pbig, size_t w, const uint64_t* qbig,
@@ -524,9 +510,8 @@ rg_status rg_poly_modswitch_dev(const rg_field* f, size_t n, const uint64_t* d_p
   if (qz || (qbig[w - 1] >> 63)) return RG_ERR_INVALID;  // qBig > 0, as a w-word signed value
   if (n == 0) return RG_OK;
   hipStream_t st = as_stream(stream);
-#define RG_MS(L) modswitch_L<L>(f, d_pbig, (int)w, qbig, d_out, (long long)n, st)
-  RG_DISPATCH_L(f->L, RG_MS)
-#undef RG_MS
+  return dispatch_limbs(f->L,
+                        [&](auto Lc) { return modswitch_L<Lc()>(f, d_pbig, (int)w, qbig, d_out, (long long)n, st); });
 }
 
 size_t rg_poly_evaluate_scratch_bytes(const rg_field* f, size_t n) {

@@ -109,8 +109,7 @@ template <int L>
 static rg_status vec_L(const rg_field* f, int op, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t n,
                        hipStream_t st) {
   VecArgs<L> v;
-  memcpy(v.F.q, f->q, 8 * L);
-  v.F.qinv = f->qinv;
+  v.F = field_params<L>(f);
   v.out = out;
   v.a = a;
   v.b = b;
@@ -142,14 +141,7 @@ rg_status rg_vec_dev(const rg_field* f, int op, uint64_t* d_out, const uint64_t*
   if (n == 0) return RG_OK;
   if (!d_out || !d_a || (op != RG_VEC_NEG && !d_b)) return RG_ERR_INVALID;
   hipStream_t st = as_stream(stream);
-  switch (f->L) {
-    case 1: return vec_L<1>(f, op, d_out, d_a, d_b, n, st);
-    case 2: return vec_L<2>(f, op, d_out, d_a, d_b, n, st);
-    case 4: return vec_L<4>(f, op, d_out, d_a, d_b, n, st);
-    case 7: return vec_L<7>(f, op, d_out, d_a, d_b, n, st);
-    case 14: return vec_L<14>(f, op, d_out, d_a, d_b, n, st);
-    default: return RG_ERR_UNSUPPORTED;
-  }
+  return dispatch_limbs(f->L, [&](auto Lc) { return vec_L<Lc()>(f, op, d_out, d_a, d_b, n, st); });
 }
 
 rg_status rg_vec(const rg_field* f, int op, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t n) {
