@@ -141,6 +141,21 @@ rg_status rg_poly_evaluate_dev(const rg_field* f, const uint64_t* d_p, size_t n,
                                uint64_t* d_scratch, void* stream);
 size_t rg_poly_evaluate_scratch_bytes(const rg_field* f, size_t n);
 rg_status rg_poly_evaluate(const rg_field* f, const uint64_t* p, size_t n, const uint64_t* x, uint64_t* out);
+/* Poly.Evaluate(x) of `batch` polynomials at ONE point (evals[i] = Poly(v[i]).Evaluate(x),
+ * jindo/prover.go:318-321): polynomial b starts at element b * stride of d_p and its first n
+ * coefficients are evaluated (stride >= n; elements [n, stride) are never read, so a prefix of
+ * a longer polynomial, such as Buckler's comPolys inside their embedRank buffers, is evaluated
+ * in place).  d_out [batch][L]; n = 0 gives 0.  d_scratch holds
+ * rg_poly_evaluate_batch_scratch_bytes(f, n, batch) bytes.  A workgroup per tile of 4096
+ * coefficients reads them coalesced and the tile sums fold per polynomial; no atomics, so the
+ * result does not depend on scheduling.  RG_ERR_UNSUPPORTED for a limb count other than
+ * 1, 2, 4, 7, 14; RG_ERR_INVALID for stride < n or a NULL buffer; batch = 0 does nothing.
+ * The host form reads (batch - 1) * stride + n elements of p. */
+size_t rg_poly_evaluate_batch_scratch_bytes(const rg_field* f, size_t n, size_t batch);
+rg_status rg_poly_evaluate_batch_dev(const rg_field* f, const uint64_t* d_p, size_t n, size_t stride, size_t batch,
+                                     const uint64_t* d_x, uint64_t* d_out, void* d_scratch, void* stream);
+rg_status rg_poly_evaluate_batch(const rg_field* f, const uint64_t* p, size_t n, size_t stride, size_t batch,
+                                 const uint64_t* x, uint64_t* out);
 /* CyclotomicEvaluator.ModSwitchTo(pOut, pBig, qBig) (cyclotomic.go:97-124) on n coefficients:
  * pBig[i] as w little-endian words of a two's-complement integer ([n][w], |pBig[i]| < 2^(64w-1);
  * Go's big.Int values, e.g. PolyToBigintCentered output), qBig as w words (host, 0 < qBig <
@@ -486,10 +501,13 @@ rg_status rg_uniform_words_dev(const uint8_t* seed, size_t seed_len, unsigned lo
                                unsigned long long first_word, size_t n, uint64_t* d_out, void* stream);
 
 /* Prover.Evaluate (prover.go:205-324), device-resident, with the Fiat-Shamir challenges
- * INJECTED: the transcript (SHAKE128 over CommitKey/Commitment/Proof serializations),
- * encodeChallengeTo, leftVec/encode and Poly.Evaluate stay in the Go caller, which also keeps
- * the shape panics (:206-216).  Challenge polynomials are ringQ / ringQOut residues in the
- * NTT + Montgomery domain, as Go holds them; every product is MulCoeffsMontgomeryThenAdd.
+ * INJECTED: the transcript (SHAKE128 over CommitKey/Commitment/Proof serializations) stays in
+ * the Go caller, which also keeps the shape panics (:206-216).  What it derives from the
+ * transcript's bytes is built on the device: the challenge polynomials by
+ * rg_jindo_encode_challenges_dev, encode(leftVec(x)) by rg_jindo_eval_point_dev and the
+ * evaluations by rg_poly_evaluate_batch_dev (below).  Challenge polynomials are ringQ / ringQOut
+ * residues in the NTT + Montgomery domain, as Go holds them; every product is
+ * MulCoeffsMontgomeryThenAdd.
  * 1. openBatch = sum_i open[i] * batch[i] (:228-266); with d_bq = d_bo = NULL (params.batch == 1,
  *    batch must be 1) openBatch = open[0] (:267-269).  A GPU holding a shard of a batch passes its
  *    openings and their challenges; the shards' openBatches sum across GPUs (RCCL all-reduce of
@@ -514,11 +532,32 @@ rg_status rg_jindo_eval_partial_dev(const rg_jindo* j, const uint64_t* d_ob_enc,
  *      d_chals [cols][nq][d]   d_pf_enc [rows][nq][d]   d_pf_mlwe [in_msis+mlwe][nq][d]          */
 rg_status rg_jindo_eval_respond_dev(const rg_jindo* j, const uint64_t* d_ob_enc, const uint64_t* d_ob_mlwe,
                                     const uint64_t* d_chals, uint64_t* d_pf_enc, uint64_t* d_pf_mlwe, void* stream);
+/* The evaluation point's vectors (utils.go:63-82), from x (one Montgomery element on the device):
+ *   d_left  [rows][nq][d]  Encoder.encode([leftVec(x)[j]]) (encoder.go:105-146) for every row j:
+ *           leftVec[j] = (x^(cols slots))^j, then leftVec[rows-1] = x; digit i of the plain value at
+ *           coefficient i * slots, every other coefficient zero, MFormLazy and NTT per prime -- word
+ *           for word what Commit produces for that element in slot 0 of an otherwise empty row
+ *   d_right [cols*slots][L]  rightVec(x)[i] = x^i; NULL: not written (Evaluate needs d_left only)
+ * Any shape rg_jindo_create accepts.  Asynchronous on `stream`. */
+rg_status rg_jindo_eval_point_dev(const rg_jindo* j, const uint64_t* d_x, uint64_t* d_left, uint64_t* d_right,
+                                  void* stream);
+/* encodeChallengeTo (utils.go:20-46) of n challenges into ringQ (ring = 0) or ringQOut (ring = 1):
+ * d_bytes [n][16], the transcript's bytes of each challenge (two big-endian words, the first the
+ * low word); exp successive remainders by ChallengeBound, a remainder r > bound / 2 stored as
+ * q_l - (bound - r), at coefficients i * slots; MForm and NTT.  d_out [n][nq or nqo][d].
+ * ChallengeBound = 1 gives zero polynomials, as in the reference.  RG_ERR_INVALID for another
+ * `ring`, and where ChallengeBound is 0 (exp > 120), the reference's division by zero. */
+rg_status rg_jindo_encode_challenges_dev(const rg_jindo* j, int ring, const uint8_t* d_bytes, size_t n,
+                                         uint64_t* d_out, void* stream);
+/* Parameters.ChallengeBound() (params.go:357-360): min(base, 1 << (120 / exp)) / 2.  RG_ERR_INVALID
+ * (with the reason in rg_last_error) where it is 0. */
+rg_status rg_jindo_challenge_bound(const rg_jindo_params* p, uint64_t* bound);
 
 /* Verifier.Verify (verifier.go:50-282), device-resident, with the Fiat-Shamir challenges
  * INJECTED as in Evaluate: the caller replays the transcript (SHAKE128 over the commit key,
- * commitments, x, Proof.Partial; :56-96), encodes the challenges (encodeChallengeTo), computes
- * leftVec/encode and rightVec (utils.go:63-82) and keeps the shape panics (:51-54).
+ * commitments, x, Proof.Partial; :56-96) and keeps the shape panics (:51-54); the challenge
+ * polynomials, encode(leftVec(x)) and rightVec(x) (utils.go:20-82) come from
+ * rg_jindo_encode_challenges_dev and rg_jindo_eval_point_dev on the transcript's bytes.
  *   d_com   [batch][out_msis][nq][d]  the commitments (rg_jindo_commit_dev layout)
  *   d_bq, d_bo [batch][nq][d], [batch][nqo][d]  batch[i] / batchOut[i]; NULL when batch == 1
  *   d_chals [cols][nq][d]   d_left [rows][nq][d] (encode(leftVec(x)[j]))

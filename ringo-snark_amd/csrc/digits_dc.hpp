@@ -31,6 +31,19 @@ struct DigitDc {
   int exp;                      // 16 (L = 4), 8 (L = 2), 0: the general loop
 };
 
+// (num = r * 2^32 + chunk) / b with the precomputed reciprocal binv = floor(2^64 / b), r < b < 2^32:
+// the quotient (< 2^32), the remainder in r
+RG_HD uint32_t divstep(uint64_t num, uint64_t b, uint64_t binv, uint64_t& r) {
+  uint64_t qt = mul_hi(num, binv);
+  uint64_t rem = num - qt * b;
+  if (rem >= b) {
+    rem -= b;
+    ++qt;
+  }
+  r = rem;
+  return (uint32_t)qt;
+}
+
 RG_HD uint32_t dc_umulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
 
 // (r 2^32 + n0) / B2 for r < B2, B2 in (2^31, 2^32): floor(2^64 / B2) = 2^32 + B0, so

@@ -55,24 +55,6 @@ __device__ __forceinline__ uint64_t signed_residue(long long c, uint64_t q) {
   return a < q ? q - a : q - a % q;
 }
 
-// d-point negacyclic NTT (Lattigo ordering: natural -> bit-reversed) of one limb held in LDS,
-// by `nt` threads (thread index `ti`); synchronises the whole workgroup between stages.
-__device__ void ntt_lds(uint64_t* p, int d, const ulonglong2* roots, uint64_t q, int ti, int nt, bool active) {
-  int lt = 0;
-  while ((2 << lt) < d) ++lt;  // log2(d/2)
-  for (int m = 1, t = d >> 1; m < d; m <<= 1, t >>= 1, --lt) {
-    if (active) {
-      for (int k = ti; k < (d >> 1); k += nt) {
-        const int i = k >> lt, j = (i << (lt + 1)) + (k & (t - 1));
-        const ulonglong2 w = roots[m + i];
-        const uint64_t u = p[j], v = sh_mul(p[j + t], w.x, w.y, q);
-        p[j] = mod_add(u, v, q);
-        p[j + t] = mod_sub(u, v, q);
-      }
-    }
-    __syncthreads();
-  }
-}
 // ------------------------------------------------------------------------------------------
 // 1. digits
 // ------------------------------------------------------------------------------------------
@@ -98,19 +80,7 @@ struct DigitArgs {
   IdxDiv d_slots, d_rows, d_cols1;  // total < 2^32: the index split by idx_div (else 64-bit division)
 };
 
-// (num = r * 2^32 + chunk) / b with the precomputed reciprocal, r < b < 2^32
-__device__ __forceinline__ uint32_t divstep(uint64_t num, uint64_t b, uint64_t binv, uint64_t& r) {
-  uint64_t qt = mul_hi(num, binv);
-  uint64_t rem = num - qt * b;
-  if (rem >= b) {
-    rem -= b;
-    ++qt;
-  }
-  r = rem;
-  return (uint32_t)qt;
-}
-
-// the same step for a divisor d in (2^31, 2^32) (b^2 of every configs field: 60272^2, 60256^2),
+// divstep's step (digits_dc.hpp) for a divisor d in (2^31, 2^32) (b^2 of every configs field: 60272^2, 60256^2),
 // whose reciprocal is 2^32 + B0: hi64(num (2^32 + B0)) = r + hi32(r B0 + n0 + hi32(n0 B0)) for
 // num = r 2^32 + n0 -- three 32-bit multiplies instead of a 64 x 64 high product and a 64-bit
 // product
@@ -124,44 +94,6 @@ __device__ __forceinline__ uint32_t divstep_b2(uint32_t r, uint32_t n0, uint32_t
   }
   rem = (uint32_t)rm;
   return qt;
-}
-
-// x R^-1 mod q (Slice = fromMont, element.go): Montgomery reduction alone, L^2 word products
-// instead of the 2 L^2 of f_mul(x, 1).  For any x < R, (x + m q) / R < q + 1, so one conditional
-// subtraction of q leaves the canonical residue (a non-canonical word such as x = q gives 0, as
-// f_mul(x, 1) did).
-template <int L>
-__device__ __forceinline__ void f_redc(uint64_t* z, const uint64_t* x, const FieldParams<L>& F) {
-  uint64_t t[L];
-#pragma unroll
-  for (int i = 0; i < L; ++i) t[i] = x[i];
-#pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const uint64_t m = t[0] * F.qinv;
-    uint64_t lo, hi;
-    mul_wide(m, F.q[0], lo, hi);
-    uint32_t c0 = 0;
-    addc(lo, t[0], c0);  // == 0 mod 2^64; only the carry is kept
-    uint64_t carry = hi + c0;
-#pragma unroll
-    for (int j = 1; j < L; ++j) {
-      mul_wide(m, F.q[j], lo, hi);
-      uint32_t c = 0;
-      lo = addc(lo, t[j], c);
-      hi += c;
-      c = 0;
-      lo = addc(lo, carry, c);
-      t[j - 1] = lo;
-      carry = hi + c;
-    }
-    t[L - 1] = carry;
-  }
-  uint64_t d[L];
-  uint32_t br = 0;
-#pragma unroll
-  for (int i = 0; i < L; ++i) d[i] = subb(t[i], F.q[i], br);
-#pragma unroll
-  for (int i = 0; i < L; ++i) z[i] = br ? t[i] : d[i];
 }
 
 template <int L>
@@ -2071,10 +2003,7 @@ static rg_status launch_digits(const rg_jindo* J, size_t batch, const uint64_t* 
   const uint64_t b2 = (uint64_t)J->p.base * J->p.base;
   a.b2 = (b2 >> 32) ? 0 : b2;
   a.b2_inv = a.b2 ? (uint64_t)(((unsigned __int128)1 << 64) / b2) : 0;
-  int qbits = 0;
-  for (int l = L - 1; l >= 0 && !qbits; --l)
-    if (J->field.q[l]) qbits = 64 * l + 64 - __builtin_clzll(J->field.q[l]);
-  a.dc = dc_constants((uint64_t)J->p.base, J->p.exp, L, qbits);
+  a.dc = dc_constants((uint64_t)J->p.base, J->p.exp, L, field_bits(J->field));
   a.v = v;
   a.last_row = last;
   a.mask = mask;

@@ -55,6 +55,63 @@ __device__ __forceinline__ uint64_t sh_mul(uint64_t y, uint64_t w, uint64_t wp, 
   return shoup_mul(y, w, wp, q);
 }
 
+// x R^-1 mod q (Slice = fromMont, element.go): Montgomery reduction alone, L^2 word products
+// instead of the 2 L^2 of f_mul(x, 1).  For any x < R, (x + m q) / R < q + 1, so one conditional
+// subtraction of q leaves the canonical residue (a non-canonical word such as x = q gives 0, as
+// f_mul(x, 1) did).
+template <int L>
+__device__ __forceinline__ void f_redc(uint64_t* z, const uint64_t* x, const FieldParams<L>& F) {
+  uint64_t t[L];
+#pragma unroll
+  for (int i = 0; i < L; ++i) t[i] = x[i];
+#pragma unroll
+  for (int i = 0; i < L; ++i) {
+    const uint64_t m = t[0] * F.qinv;
+    uint64_t lo, hi;
+    mul_wide(m, F.q[0], lo, hi);
+    uint32_t c0 = 0;
+    addc(lo, t[0], c0);  // == 0 mod 2^64; only the carry is kept
+    uint64_t carry = hi + c0;
+#pragma unroll
+    for (int j = 1; j < L; ++j) {
+      mul_wide(m, F.q[j], lo, hi);
+      uint32_t c = 0;
+      lo = addc(lo, t[j], c);
+      hi += c;
+      c = 0;
+      lo = addc(lo, carry, c);
+      t[j - 1] = lo;
+      carry = hi + c;
+    }
+    t[L - 1] = carry;
+  }
+  uint64_t d[L];
+  uint32_t br = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) d[i] = subb(t[i], F.q[i], br);
+#pragma unroll
+  for (int i = 0; i < L; ++i) z[i] = br ? t[i] : d[i];
+}
+
+// d-point negacyclic NTT (Lattigo ordering: natural -> bit-reversed) of one limb held in LDS,
+// by `nt` threads (thread index `ti`); synchronises the whole workgroup between stages.
+__device__ inline void ntt_lds(uint64_t* p, int d, const ulonglong2* roots, uint64_t q, int ti, int nt, bool active) {
+  int lt = 0;
+  while ((2 << lt) < d) ++lt;  // log2(d/2)
+  for (int m = 1, t = d >> 1; m < d; m <<= 1, t >>= 1, --lt) {
+    if (active) {
+      for (int k = ti; k < (d >> 1); k += nt) {
+        const int i = k >> lt, j = (i << (lt + 1)) + (k & (t - 1));
+        const ulonglong2 w = roots[m + i];
+        const uint64_t u = p[j], v = sh_mul(p[j + t], w.x, w.y, q);
+        p[j] = mod_add(u, v, q);
+        p[j + t] = mod_sub(u, v, q);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // d-point inverse negacyclic NTT (GS, bit-reversed -> natural), times d^-1, of one limb held in
 // LDS, by `nt` threads (thread index `ti`); synchronises the whole workgroup between stages
 __device__ inline void intt_lds(uint64_t* p, int d, const ulonglong2* roots, const RnsPrime& P, int ti, int nt,
@@ -209,6 +266,7 @@ struct rg_jindo_scratch {
   rg::DevBuf digits, com, ocom;
   rg::DevBuf last, mask, en, mn;  // the sampled randomness of rg_jindo_commit_sampled_dev
   rg::DevBuf wq;                  // cdt2_noise_kernel's chunk counter
+  rg::DevBuf point;               // rg_jindo_eval_point_dev: x^0 .. x^(cols slots), then leftVec [rows]
 };
 
 // Sampler setup (rg_jindo_set_stddevs): the reference's six standard deviations and the tables
@@ -255,6 +313,13 @@ struct rg_jindo {
 };
 
 namespace rg {
+
+// bit length of the field modulus
+inline int field_bits(const rg_field& f) {
+  for (int l = f.L - 1; l >= 0; --l)
+    if (f.q[l]) return 64 * l + 64 - __builtin_clzll(f.q[l]);
+  return 0;
+}
 
 // jindo.hip
 RingDev ring_dev(const RnsPrime* P, int n, const DevBuf& f, const DevBuf& b);

@@ -3,11 +3,16 @@
 // Evaluate: every MulCoeffsMontgomeryThenAdd loop is a J = 1 dot product on mac_kernel
 // (rg_jindo_eval_*; dot_split_kernel for the batch combination), plus rns_reduce_kernel after a
 // cross-GPU sum of partial openBatches.
+// The inputs of both that depend on the transcript alone are built here too: leftVec / rightVec of
+// the evaluation point with Encoder.encode of each left element (rg_jindo_eval_point_dev) and
+// encodeChallengeTo of the challenge bytes (rg_jindo_encode_challenges_dev).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "chal_digits.hpp"
+#include "digits_dc.hpp"
 #include "host_field.hpp"
 #include "jindo_impl.hpp"
 
@@ -304,6 +309,146 @@ __global__ __launch_bounds__(256) void rns_reduce_kernel(uint64_t* x, long long 
   if (i >= npoly * nl * d) return;
   const RnsPrime& P = R.p[(int)((i / d) % nl)];
   x[i] = sh_mul(x[i], 1, P.one_sh, P.q);
+}
+
+// ------------------------------------------------------------------------------------------
+// The inputs Evaluate and Verify derive from the transcript (jindo/utils.go:20-82):
+//   encode_left_kernel  workgroup per row j of leftVec: one lane takes the element out of Montgomery
+//                       form and expands its base-b digits into coefficients i * slots
+//                       (Encoder.encode of a one-element vector, encoder.go:105-146: slot 0 of an
+//                       otherwise empty row, every other coefficient zero), MForm, then the NTT per
+//                       ring prime -- the commit path's digits_kernel + prep_kernel for that element
+//                       without noise
+//   encode_chal_kernel  workgroup per challenge: one lane takes exp remainders of the 128-bit value
+//                       by ChallengeBound (divMod64, utils.go:12-18), signs them, MForm, NTT
+// ------------------------------------------------------------------------------------------
+// NTT per limb of poly [R.n][d] in LDS (two limbs at a time on the halves of the workgroup, as
+// prep_kernel), then the store; the caller has synchronised after filling poly
+__device__ inline void ntt_store(uint64_t* poly, const RingDev& R, int d, uint64_t* dst) {
+  const int tid = threadIdx.x, half = blockDim.x >> 1;
+  for (int l0 = 0; l0 < R.n; l0 += 2) {
+    const int l = l0 + (tid >= half ? 1 : 0);
+    const bool active = l < R.n;
+    const int lc = active ? l : l0;
+    ntt_lds(poly + (long long)lc * d, d, R.fwd + (long long)lc * d, R.p[lc].q, tid % half, half, active);
+  }
+  for (int k = tid; k < R.n * d; k += blockDim.x) dst[k] = poly[k];
+}
+
+template <int L>
+struct PointArgs {
+  int d, slots, exp, rows;
+  RingDev R;
+  FieldParams<L> F;
+  uint64_t base, base_inv;  // b and floor(2^64 / b)
+  DigitDc dc;               // digits_dc.hpp constants; dc.exp != exp: the division loop
+  const uint64_t* lp;       // [rows][L] skip^j
+  const uint64_t* x;        // the point: left[rows - 1]
+  uint64_t* out;            // [rows][R.n][d]
+};
+
+template <int L>
+__global__ __launch_bounds__(256) void encode_left_kernel(PointArgs<L> a) {
+  extern __shared__ uint64_t poly_lds[];
+  const int d = a.d, tid = threadIdx.x, nl = a.R.n, row = blockIdx.x;
+  for (int k = tid; k < nl * d; k += blockDim.x) poly_lds[k] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    // left[rows - 1] = x is written last (utils.go:70), also when skip^(rows-1) was there
+    const uint64_t* e = row == a.rows - 1 ? a.x : a.lp + (long long)row * L;
+    uint64_t xv[L], c[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) xv[l] = e[l];
+    f_redc<L>(c, xv, a.F);  // Slice = fromMont
+    auto put = [&](int j, uint32_t dg) {  // MForm(digit) at coefficient j * slots (digit < 2^32 <= any word)
+      for (int l = 0; l < nl; ++l) {
+        const RnsPrime& P = a.R.p[l];
+        poly_lds[(long long)l * d + j * a.slots] = sh_mul(dg, P.r64, P.r64_sh, P.q);
+      }
+    };
+    bool done = false;
+    if constexpr (L == 4 || L == 2) {
+      if (a.dc.exp == a.exp) {
+        dc_digits<L>(c, a.dc, put);
+        done = true;
+      }
+    }
+    if (!done) {  // exp - 1 remainders, then the last quotient (encoder.go:125-136)
+      uint32_t w[2 * L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        w[2 * l] = (uint32_t)c[l];
+        w[2 * l + 1] = (uint32_t)(c[l] >> 32);
+      }
+      for (int jd = 0; jd < a.exp - 1; ++jd) {
+        uint64_t rem = 0;
+        for (int k = 2 * L - 1; k >= 0; --k) w[k] = divstep((rem << 32) | w[k], a.base, a.base_inv, rem);
+        put(jd, (uint32_t)rem);
+      }
+      put(a.exp - 1, w[0]);
+    }
+  }
+  __syncthreads();
+  ntt_store(poly_lds, a.R, d, a.out + (long long)row * nl * d);
+}
+
+struct ChalArgs {
+  int d, slots, exp;
+  RingDev R;
+  uint64_t bound, bound_inv;  // ChallengeBound >= 1 and floor(2^64 / bound) (unused when bound = 1)
+  const uint8_t* bytes;       // [n][16]
+  uint64_t* out;              // [n][R.n][d]
+};
+
+__global__ __launch_bounds__(256) void encode_chal_kernel(ChalArgs a) {
+  extern __shared__ uint64_t poly_lds[];
+  const int d = a.d, tid = threadIdx.x, nl = a.R.n;
+  for (int k = tid; k < nl * d; k += blockDim.x) poly_lds[k] = 0;
+  __syncthreads();
+  if (tid == 0 && a.bound > 1) {  // bound = 1: every remainder is 0 (utils.go:31-32)
+    chal_digits(a.bytes + (long long)blockIdx.x * 16, a.bound, a.bound_inv, a.exp, [&](int i, uint64_t r, bool neg) {
+      for (int l = 0; l < nl; ++l) {
+        const RnsPrime& P = a.R.p[l];
+        const uint64_t v = neg ? P.q - (a.bound - r) : r;
+        poly_lds[(long long)l * d + i * a.slots] = sh_mul(v, P.r64, P.r64_sh, P.q);  // MForm
+      }
+    });
+  }
+  __syncthreads();
+  ntt_store(poly_lds, a.R, d, a.out + (long long)blockIdx.x * nl * d);
+}
+
+// leftVec's powers live in the stream's scratch: x^0 .. x^(cols slots), then skip^0 .. skip^(rows-1)
+static rg_status point_scratch(rg_jindo* J, hipStream_t st, uint64_t** out) {
+  const rg_jindo_params& p = J->p;
+  std::lock_guard<std::mutex> lk(J->mu);
+  std::unique_ptr<rg_jindo_scratch>& S = J->scratch[st];
+  if (!S) S.reset(new rg_jindo_scratch());
+  RG_TRY(S->point.alloc(((size_t)p.cols * p.slots + 1 + p.rows) * p.field_limbs * 8));
+  *out = S->point.as<uint64_t>();
+  return RG_OK;
+}
+
+template <int L>
+static rg_status launch_encode_left(const rg_jindo* J, const uint64_t* lp, const uint64_t* x, uint64_t* out,
+                                    hipStream_t st) {
+  const rg_jindo_params& p = J->p;
+  PointArgs<L> a;
+  memset(&a, 0, sizeof(a));
+  a.d = p.d;
+  a.slots = p.slots;
+  a.exp = p.exp;
+  a.rows = p.rows;
+  a.R = ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b);
+  a.F = field_params<L>(&J->field);
+  a.base = p.base;
+  a.base_inv = J->base_inv;
+  a.dc = dc_constants((uint64_t)p.base, p.exp, L, field_bits(J->field));
+  a.lp = lp;
+  a.x = x;
+  a.out = out;
+  hipLaunchKernelGGL(encode_left_kernel<L>, dim3((unsigned)p.rows), dim3(256), (size_t)p.nq * p.d * 8, st, a);
+  return check_launch("jindo encode left");
 }
 
 }  // namespace rg
@@ -610,6 +755,77 @@ rg_status rg_jindo_verify_dev(const rg_jindo* J, size_t batch, const uint64_t* d
   res->eval_ok = memcmp(res->eval_lhs, res->eval_rhs, 8 * L) == 0;
   res->ok = res->outer_ok && res->inner_ok && res->consistency_ok && res->eval_ok;
   return RG_OK;
+}
+
+// ---- the transcript-derived inputs of Evaluate and Verify (utils.go:20-82) -------------------
+rg_status rg_jindo_challenge_bound(const rg_jindo_params* p, uint64_t* bound) {
+  if (!p || !bound) {
+    set_last_error("jindo challenge bound: NULL argument");
+    return RG_ERR_INVALID;
+  }
+  if (p->exp < 1 || p->base < 2) {
+    set_last_error("jindo challenge bound: exp < 1 or base < 2");
+    return RG_ERR_INVALID;
+  }
+  *bound = challenge_bound(p->base, p->exp);
+  if (*bound == 0) {  // the reference divides by zero (utils.go:12-18)
+    set_last_error("jindo challenge bound: ChallengeBound() = min(base, 1 << (120 / exp)) / 2 is 0 at exp = " +
+                   std::to_string(p->exp) + " (exp > 120 or 120 / exp >= 64)");
+    return RG_ERR_INVALID;
+  }
+  return RG_OK;
+}
+
+rg_status rg_jindo_eval_point_dev(const rg_jindo* J, const uint64_t* d_x, uint64_t* d_left, uint64_t* d_right,
+                                  void* stream) {
+  if (!J || !d_x || !d_left) {
+    set_last_error("jindo eval point: NULL handle, point or left buffer");
+    return RG_ERR_INVALID;
+  }
+  RG_TRY(on_device(J));
+  const rg_jindo_params& p = J->p;
+  const size_t cs = (size_t)p.cols * p.slots, L = p.field_limbs;
+  hipStream_t st = as_stream(stream);
+  uint64_t* pw = nullptr;
+  RG_TRY(point_scratch(const_cast<rg_jindo*>(J), st, &pw));
+  uint64_t* lp = pw + (cs + 1) * L;
+  // rightVec: right[i] = x^i (utils.go:75-82); one more power is leftVec's skip = x^(cols slots)
+  RG_TRY(rg_buckler_powers_dev(&J->field, d_x, cs + 1, pw, stream));
+  if (d_right) RG_HIP(hipMemcpyAsync(d_right, pw, cs * L * 8, hipMemcpyDeviceToDevice, st));
+  // leftVec: left[i] = skip^i, then left[rows - 1] = x (utils.go:63-72; the kernel takes x for that row)
+  RG_TRY(rg_buckler_powers_dev(&J->field, pw + cs * L, p.rows, lp, stream));
+  return dispatch_limbs((int)L, [&](auto Lc) { return launch_encode_left<Lc()>(J, lp, d_x, d_left, st); });
+}
+
+rg_status rg_jindo_encode_challenges_dev(const rg_jindo* J, int ring, const uint8_t* d_bytes, size_t n,
+                                         uint64_t* d_out, void* stream) {
+  if (ring != 0 && ring != 1) {
+    set_last_error("jindo encode challenges: ring " + std::to_string(ring) + " is neither 0 (ringQ) nor 1 (ringQOut)");
+    return RG_ERR_INVALID;
+  }
+  if (!J || (n && (!d_bytes || !d_out))) {
+    set_last_error("jindo encode challenges: NULL handle or buffer");
+    return RG_ERR_INVALID;
+  }
+  if (n > 0x7fffffffull) {
+    set_last_error("jindo encode challenges: n out of range");
+    return RG_ERR_INVALID;
+  }
+  const rg_jindo_params& p = J->p;
+  ChalArgs a;
+  memset(&a, 0, sizeof(a));
+  RG_TRY(rg_jindo_challenge_bound(&p, &a.bound));
+  if (n == 0) return RG_OK;
+  RG_TRY(on_device(J));
+  a.d = p.d;
+  a.slots = p.slots;
+  a.exp = p.exp;
+  a.R = ring ? ring_dev(J->ro, p.nqo, J->rootso_f, J->rootso_b) : ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b);
+  a.bound_inv = a.bound > 1 ? (uint64_t)(((unsigned __int128)1 << 64) / a.bound) : 0;
+  a.bytes = d_bytes;
+  a.out = d_out;
+  hipLaunchKernelGGL(encode_chal_kernel, dim3((unsigned)n), dim3(256), (size_t)a.R.n * p.d * 8, as_stream(stream), a);
+  return check_launch("jindo encode challenges");
 }
 
 rg_status rg_jindo_eval_reduce_dev(const rg_jindo* J, uint64_t* d_ob_incom, uint64_t* d_ob_enc, uint64_t* d_ob_mlwe,

@@ -76,6 +76,11 @@ _SIGS = {
     "rg_poly_evaluate_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, vp, vp, vp]),
     "rg_poly_evaluate_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
     "rg_poly_evaluate": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, u64p, u64p]),
+    "rg_poly_evaluate_batch_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t, ctypes.c_size_t]),
+    "rg_poly_evaluate_batch_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp,
+                                                  vp]),
+    "rg_poly_evaluate_batch": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p,
+                                              u64p]),
     "rg_poly_modswitch_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, u64p, vp, vp]),
     "rg_poly_modswitch": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p]),
     "rg_buckler_encode_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp, vp, vp]),
@@ -160,6 +165,9 @@ _SIGS = {
     "rg_jindo_eval_partial_dev": (ctypes.c_int, [vp, vp, vp, vp, vp]),
     "rg_jindo_eval_reduce_dev": (ctypes.c_int, [vp, vp, vp, vp, vp]),
     "rg_jindo_eval_respond_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "rg_jindo_eval_point_dev": (ctypes.c_int, [vp, vp, vp, vp, vp]),
+    "rg_jindo_encode_challenges_dev": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp]),
+    "rg_jindo_challenge_bound": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), ctypes.POINTER(ctypes.c_uint64)]),
     "rg_jindo_verify_dev": (ctypes.c_int, [vp, ctypes.c_size_t] + [vp] * 11 + [ctypes.c_double, ctypes.c_double, vp,
                                                                             vp]),
     "rg_malloc": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_size_t]),

@@ -424,6 +424,44 @@ def NewCyclicEvaluator(field, rank):
     return CyclicEvaluator(field, rank, CyclicTransformer(field, rank))
 
 
+def evaluate_batch_scratch_bytes(field, n, batch):
+    """Bytes of device scratch evaluate_batch_dev needs (rg_poly_evaluate_batch_scratch_bytes)."""
+    return lib().rg_poly_evaluate_batch_scratch_bytes(field.h, n, batch)
+
+
+def evaluate_batch_dev(field, d_p, n, stride, batch, d_x, d_out, d_scratch, stream=None):
+    """rg_poly_evaluate_batch_dev: Poly.Evaluate (poly.go:64-76) of `batch` device-resident
+    polynomials at the one point d_x.  Polynomial b is the first n coefficients at element
+    b * stride of d_p (stride >= n); d_out [batch][L]; d_scratch of evaluate_batch_scratch_bytes."""
+    if stride < n:
+        raise RingoPanic("inconsistent input(s)")
+    L = field.L
+    pw = ((batch - 1) * stride + n) * L if batch and n else None
+    sw = (evaluate_batch_scratch_bytes(field, n, batch) + 7) // 8
+    check(lib().rg_poly_evaluate_batch_dev(field.h, _addr(d_p, pw) if n else _addr(d_p), n, stride, batch,
+                                           _addr(d_x, L), _addr(d_out, batch * L), _addr(d_scratch, sw),
+                                           _stream(stream)))
+
+
+def EvaluateBatch(polys, x):
+    """[p.Evaluate(x) for p in polys] in one call (rg_poly_evaluate_batch): polys of one field and
+    rank, coefficient domain; returns [len(polys)][L]."""
+    polys = list(polys)
+    if not polys:
+        raise RingoPanic("inconsistent input(s)")
+    field, n = polys[0].field, polys[0].Rank()
+    for p in polys:
+        if p.IsNTT:
+            raise RingoPanic("Evaluate: p is in NTT form")
+        if p.Rank() != n or p.field.L != field.L:
+            raise RingoPanic("inconsistent input(s)")
+    co = np.ascontiguousarray(np.stack([p.Coeffs for p in polys]), np.uint64)
+    out = np.zeros((len(polys), field.L), np.uint64)
+    xx = np.ascontiguousarray(x, np.uint64).reshape(field.L)
+    check(lib().rg_poly_evaluate_batch(field.h, ptr(co), n, n, len(polys), ptr(xx), ptr(out)))
+    return out
+
+
 def vec_dev(field, op, d_out, d_a, d_b, n, stream=None):
     """rg_vec_dev: device-resident pointwise op over n elements."""
     w = n * field.L

@@ -277,8 +277,9 @@ class Prover:
 
 
     # ---- Prover.Evaluate (jindo/prover.go:205-324), device-resident, challenges injected ----
-    # The Fiat-Shamir transcript, encodeChallengeTo, leftVec/encode and Poly.Evaluate stay with
-    # the caller (Go in the reference); these are its MulCoeffsMontgomeryThenAdd loops.
+    # The Fiat-Shamir transcript stays with the caller (Go in the reference); these are Evaluate's
+    # MulCoeffsMontgomeryThenAdd loops, and eval_point_dev / encode_challenges_dev (with
+    # bigpoly.evaluate_batch_dev) build their inputs from the transcript's bytes on the device.
     def eval_shapes(self):
         P = self.params
         nm = P.in_msis + P.mlwe
@@ -320,6 +321,45 @@ class Prover:
                                               _stream(stream)))
 
 
+    def eval_point_dev(self, x, left, right=None, stream=None):
+        """left [rows][nq][d] = encode(leftVec(x)[j]) and, unless None, right [cols*slots][L] =
+        rightVec(x) (utils.go:63-82) from the point x [L] on the device (rg_jindo_eval_point_dev)."""
+        P = self.params
+        check(lib().rg_jindo_eval_point_dev(self.h, _addr(x, P.L), _addr(left, P.rows * P.nq * P.d),
+                                            _addr(right, P.cols * P.slots * P.L), _stream(stream)))
+
+    def encode_challenges_dev(self, ring, bytes, n, out, stream=None):
+        """encodeChallengeTo (utils.go:20-46) of n challenges: bytes, a device buffer of n * 16 bytes
+        (a uint8 tensor or an int address), into out [n][nq or nqo][d] of ringQ (ring 0) or
+        ringQOut (ring 1) (rg_jindo_encode_challenges_dev)."""
+        P = self.params
+        if ring not in (0, 1):
+            raise RingoPanic("ring must be 0 (ringQ) or 1 (ringQOut)")
+        check(lib().rg_jindo_encode_challenges_dev(self.h, ring, _byte_addr(bytes, 16 * n), n,
+                                                   _addr(out, n * (P.nqo if ring else P.nq) * P.d), _stream(stream)))
+
+    def challenge_bound(self):
+        """Parameters.ChallengeBound() (params.go:357-360)."""
+        b, ps = ctypes.c_uint64(), self.params.c_struct()
+        check(lib().rg_jindo_challenge_bound(ctypes.byref(ps), ctypes.byref(b)))
+        return b.value
+
+
+def _byte_addr(x, nbytes):
+    """Device address of a byte buffer: a contiguous uint8 tensor on the current GPU of at least
+    nbytes, or a raw int address."""
+    if x is None or isinstance(x, int):
+        return x
+    if str(x.dtype) != "torch.uint8":
+        raise RingoPanic(f"byte buffer dtype {x.dtype}: need uint8")
+    import torch
+    if not x.is_contiguous() or x.device.type != "cuda" or x.device.index != torch.cuda.current_device():
+        raise RingoPanic("byte buffer must be contiguous and on the current GPU")
+    if x.numel() < nbytes:
+        raise RingoPanic(f"byte buffer holds {x.numel()} bytes, need {nbytes}")
+    return x.data_ptr()
+
+
 class VerifyResultC(ctypes.Structure):  # include/ringo.h rg_jindo_verify_result
     _fields_ = [("outer_norm_sq", ctypes.c_uint64 * 10), ("inner_norm_sq", ctypes.c_uint64 * 10),
                 ("outer_ok", ctypes.c_int), ("inner_ok", ctypes.c_int), ("consistency_ok", ctypes.c_int),
@@ -348,6 +388,14 @@ class Verifier:
         self.params = params
         self._p = Prover(params, crs=crs, ck=ck)
         self.h = self._p.h
+
+    def eval_point_dev(self, x, left, right=None, stream=None):
+        """encode(leftVec(x)) and rightVec(x) on the device (Prover.eval_point_dev)."""
+        self._p.eval_point_dev(x, left, right, stream)
+
+    def encode_challenges_dev(self, ring, bytes, n, out, stream=None):
+        """encodeChallengeTo of n challenges on the device (Prover.encode_challenges_dev)."""
+        self._p.encode_challenges_dev(ring, bytes, n, out, stream)
 
     def verify_dev(self, batch, com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe,
                    stream=None):
