@@ -107,7 +107,10 @@ def test_batched_device_forms(fields):
 @pytest.mark.parametrize("qbits", [2, 62, 64, 130, 255, 300, 509])
 def test_mod_switch(fields, key, qbits):
     """CyclotomicEvaluator.ModSwitch on centred inputs (the bfv example's PolyToBigintCentered,
-    examples/bfv/main.go:152-155), the range ends, exact ties and values beyond qBig."""
+    examples/bfv/main.go:152-155), the range ends, +-floor(qBig/2) and values beyond qBig.
+    +-floor(qBig/2) are the ends of the centred range of p, not ties of the division: the rounding
+    looks at |p| q mod qBig, which they put on a threshold only for -qBig/2 at an even qBig (q is
+    odd).  The real ties, for both signs and parities, are in test_gpu_polyops_synthetic.py."""
     import pyref
     q = fields[key]
     F = ringo.Field(q)
