@@ -1,7 +1,9 @@
-// jindo_impl.hpp -- what jindo.hip and jindo_verify.hip share: the device-side ring constants and
-// kernel argument structs, the __device__ helpers that kernels of both units inline (there is no
-// relocatable device code, so a kernel never calls across units), the handle, and the host
-// functions that cross units.  The pipeline overview is at the top of jindo.hip.
+// jindo_impl.hpp -- what the Jindo units (jindo_setup.hip, jindo_commit.hip, jindo_sample.hip,
+// jindo_verify.hip) share: the device-side ring constants and kernel argument structs, the
+// __device__ helpers that kernels of more than one unit inline (there is no relocatable device
+// code, so a kernel never calls across units), the handle, the byte sizes of the per-commit
+// buffers, and the host functions that cross units.  Dependencies point one way: sample -> commit
+// -> setup, verify -> commit and setup.  The pipeline overview is at the top of jindo_commit.hip.
 #pragma once
 #include <map>
 #include <memory>
@@ -48,6 +50,14 @@ struct DstDev {
   uint64_t pw[kMaxQ][4], pw_sh[kMaxQ][4];
 };
 
+// The shape of one commit as the kernels see it (shape_of below)
+struct JShape {
+  int rank, rows, cols, slots, exp, d, in_msis, out_msis, mlwe, dcmp, log_in_cut, log_out_cut;
+  int nq, nqo;
+  uint64_t base;
+  long long nv;
+};
+
 // ------------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------------
@@ -91,6 +101,23 @@ __device__ __forceinline__ void f_redc(uint64_t* z, const uint64_t* x, const Fie
   for (int i = 0; i < L; ++i) d[i] = subb(t[i], F.q[i], br);
 #pragma unroll
   for (int i = 0; i < L; ++i) z[i] = br ? t[i] : d[i];
+}
+
+// Encodes the reference does not perform (prover.go:101-105, 118-123): data rows j in
+// [1, rows-2] of column i whose first index j*cols*slots (+ i*slots) is past len(v); their
+// Opening.Encode stays zero.  The start index grows with j, so the reference's `break`
+// is the same as testing each row.
+__device__ __forceinline__ bool enc_skipped(const JShape& S, int col, int row) {
+  if (row < 1 || row > S.rows - 2) return false;
+  const long long cs = (long long)S.cols * S.slots;
+  const long long start = row * cs + (col == S.cols ? 0 : (long long)col * S.slots);
+  return start > S.nv;
+}
+
+// orders a wave's LDS accesses around a wave-private exchange (no workgroup barrier)
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
 }
 
 // d-point negacyclic NTT (Lattigo ordering: natural -> bit-reversed) of one limb held in LDS,
@@ -314,16 +341,75 @@ struct rg_jindo {
 
 namespace rg {
 
-// bit length of the field modulus
-inline int field_bits(const rg_field& f) {
-  for (int l = f.L - 1; l >= 0; --l)
-    if (f.q[l]) return 64 * l + 64 - __builtin_clzll(f.q[l]);
+// bit length of the L-word value x (0 for x = 0)
+inline int bit_length(const uint64_t* x, int L) {
+  for (int l = L - 1; l >= 0; --l)
+    if (x[l]) return 64 * l + 64 - __builtin_clzll(x[l]);
   return 0;
 }
 
-// jindo.hip
+// bit length of the field modulus
+inline int field_bits(const rg_field& f) { return bit_length(f.q, f.L); }
+
+inline JShape shape_of(const rg_jindo_params& p, long long nv) {
+  JShape s;
+  s.rank = p.rank;
+  s.rows = p.rows;
+  s.cols = p.cols;
+  s.slots = p.slots;
+  s.exp = p.exp;
+  s.d = p.d;
+  s.in_msis = p.in_msis;
+  s.out_msis = p.out_msis;
+  s.mlwe = p.mlwe;
+  s.dcmp = p.dcmp;
+  s.log_in_cut = p.log_in_cut;
+  s.log_out_cut = p.log_out_cut;
+  s.nq = p.nq;
+  s.nqo = p.nqo;
+  s.base = p.base;
+  s.nv = nv;
+  return s;
+}
+
+// Byte sizes of the per-commit buffers of `batch` commits (layouts: include/ringo.h), in one place
+// for the stream scratch, the host entry points' staging buffers and the verifier
+struct JSizes {
+  size_t digits;        // [B][cols+1][rows][d] u32
+  size_t inner, outer;  // the MACs' sums before rounding: [B][cols+1][inMSIS][nq][d], [B][outMSIS][nqo][d]
+  size_t last, mask;    // [B][cols*slots][L], [B][rows][slots][L]
+  size_t en, mn;        // the noise, i64: [B][cols+1][rows][d], [B][cols+1][nm][d] (nm = inMSIS + mlwe)
+  size_t enc, mlwe;     // Opening.Encode [B][cols+1][rows][nq][d], Opening.MLWE [B][cols+1][nm][nq][d]
+  size_t incom, com;    // Opening.InCommit [B][dcmp][nqo][d], Commitment.Value [B][outMSIS][nq][d]
+  // what stream_scratch allocates for every commit (rg_jindo_scratch_bytes)
+  size_t scratch() const { return digits + inner + outer; }
+};
+inline JSizes sizes_of(const rg_jindo_params& p, size_t batch) {
+  const size_t d = p.d, L = p.field_limbs, nm = p.in_msis + p.mlwe, c1 = batch * (p.cols + 1);
+  JSizes z;
+  z.digits = c1 * p.rows * d * 4;
+  z.inner = c1 * p.in_msis * p.nq * d * 8;
+  z.outer = batch * p.out_msis * p.nqo * d * 8;
+  z.last = batch * p.cols * p.slots * L * 8;
+  z.mask = batch * p.rows * p.slots * L * 8;
+  z.en = c1 * p.rows * d * 8;
+  z.mn = c1 * nm * d * 8;
+  z.enc = c1 * p.rows * p.nq * d * 8;
+  z.mlwe = c1 * nm * p.nq * d * 8;
+  z.incom = batch * p.dcmp * p.nqo * d * 8;
+  z.com = batch * p.out_msis * p.nq * d * 8;
+  return z;
+}
+
+// ---- jindo_setup.hip ----
 RingDev ring_dev(const RnsPrime* P, int n, const DevBuf& f, const DevBuf& b);
 rg_status on_device(const rg_jindo* J);
+// the calling stream's scratch, grown to `batch` commits
+rg_status stream_scratch(rg_jindo* J, size_t batch, hipStream_t st, rg_jindo_scratch** out);
+struct MfmaPrime;  // mac_mfma.hpp
+MfmaPrime mfma_prime(const RnsPrime& P);
+
+// ---- jindo_commit.hip ----
 rg_status launch_mac(const MacArgs& m, hipStream_t st);
 // a CRT rounding from ring Q_out (src_o) or Q into Q_out (dst_o) or Q
 RoundArgs round_args(const rg_jindo* J, bool src_o, bool dst_o, int cut, const uint64_t* in, uint64_t* out,
@@ -331,5 +417,13 @@ RoundArgs round_args(const rg_jindo* J, bool src_o, bool dst_o, int cut, const u
 rg_status launch_round(RoundArgs ra, long long npoly, hipStream_t st);
 MacArgs dot_args(const RnsPrime* P, int nl, int d, long long nout, int T, const uint64_t* A, const uint64_t* B,
                  long long b_out, long long b_term, uint64_t* out);
+// the commit's stages, as the sampled commit's stream DAG (jindo_sample.hip) schedules them
+rg_status digits_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, size_t nv, const uint64_t* d_last,
+                       const uint64_t* d_mask, uint32_t* digits, hipStream_t st);
+enum PrepPart { kPrepAll = 3, kPrepEnc = 1, kPrepMlwe = 2 };
+rg_status prep_launch(rg_jindo* J, size_t batch, size_t nv, const uint32_t* digits, const int64_t* d_en,
+                      const int64_t* d_mn, uint64_t* d_enc, uint64_t* d_mlwe, int part, hipStream_t st);
+rg_status commit_core(rg_jindo* J, size_t batch, const uint64_t* d_enc, const uint64_t* d_mlwe, uint64_t* d_incom,
+                      uint64_t* d_com, rg_jindo_scratch* sc, hipStream_t st);
 
 }  // namespace rg

@@ -1,5 +1,5 @@
 // jindo_verify.hip -- the device work of Verifier.Verify and of Prover.Evaluate (overview in
-// jindo.hip; shared definitions in jindo_impl.hpp).
+// jindo_commit.hip; shared definitions in jindo_impl.hpp).
 // Evaluate: every MulCoeffsMontgomeryThenAdd loop is a J = 1 dot product on mac_kernel
 // (rg_jindo_eval_*; dot_split_kernel for the batch combination), plus rns_reduce_kernel after a
 // cross-GPU sum of partial openBatches.
@@ -20,7 +20,7 @@ namespace rg {
 
 // ------------------------------------------------------------------------------------------
 // Verifier.Verify (verifier.go:50-282), challenges injected.  The MACs run on mac_kernel
-// (jindo.hip), the lifted inner commitments on round_kernel (cut 0, ringQOut -> ringQ);
+// (jindo_commit.hip), the lifted inner commitments on round_kernel (cut 0, ringQOut -> ringQ);
 // these kernels add:
 //   norm_kernel    workgroup per polynomial: IMForm, INTT, centred CRT, sum of squares
 //                  (verifyNorm :262-276) -> kNormW words per polynomial
@@ -637,9 +637,10 @@ rg_status rg_jindo_verify_dev(const rg_jindo* J, size_t batch, const uint64_t* d
   hipStream_t st = as_stream(stream);
   const long long n_out = p.dcmp + p.out_msis, n_in = p.rows + nm + p.in_msis;
   DevBuf a_out, b_out, c_out, lift, a_in, b_in, c_in, p1, p2, norms, flag, dcd, bd, ev;
-  RG_TRY(a_out.alloc(8 * p.out_msis * po));
-  RG_TRY(b_out.alloc(8 * p.out_msis * po));
-  RG_TRY(c_out.alloc(8 * p.out_msis * po));
+  const size_t b_outer = sizes_of(p, 1).outer;  // one commit's outer commitment in ringQOut
+  RG_TRY(a_out.alloc(b_outer));
+  RG_TRY(b_out.alloc(b_outer));
+  RG_TRY(c_out.alloc(b_outer));
   RG_TRY(lift.alloc(8 * p.dcmp * pq));
   RG_TRY(a_in.alloc(8 * p.in_msis * pq));
   RG_TRY(b_in.alloc(8 * p.in_msis * pq));

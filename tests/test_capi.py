@@ -121,3 +121,28 @@ def test_mac_kinds_argument_errors_no_gpu():
     L = _lib.lib()
     a, b = ctypes.c_int(), ctypes.c_int()
     assert L.rg_jindo_mac_kinds(None, ctypes.byref(a), ctypes.byref(b)) == -1
+
+
+def test_jindo_scratch_bytes_null_handle_no_gpu():
+    assert _lib.lib().rg_jindo_scratch_bytes(None, 3) == 0
+
+
+@pytest.mark.gpu
+def test_jindo_scratch_bytes_is_the_stream_scratch_sum():
+    """rg_jindo_scratch_bytes is the sum of the three buffers a commit stream holds (digits u32, the
+    inner and the outer MAC sums), written out here from the buffer layouts of include/ringo.h, on
+    every synthetic parameter set at batch 1 and 3.  Pure arithmetic on the parameters, but a handle
+    exists only on a device (its ring tables are uploaded at creation), hence the gpu mark."""
+    from ringo import jindo
+    from tests import jindo_synth_util as su
+    from tests.jindo_proto import random_ck
+    L = _lib.lib()
+    for name in su.NAMES:
+        P, fq = su.params(name)
+        prv = jindo.Prover(jindo.Parameters.from_dict(P, fq), ck=random_ck(P, 7))
+        c1, d, nq, nqo = P["cols"] + 1, P["d"], len(P["q"]), len(P["qo"])
+        for batch in (1, 3):
+            want = batch * c1 * P["rows"] * d * 4 + batch * c1 * P["in_msis"] * nq * d * 8 + \
+                batch * P["out_msis"] * nqo * d * 8
+            assert L.rg_jindo_scratch_bytes(prv.h, batch) == want, (name, batch)
+        assert L.rg_jindo_scratch_bytes(prv.h, 0) == 0

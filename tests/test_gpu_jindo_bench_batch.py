@@ -2,7 +2,7 @@
 (t14_b1, 256 commits per step) and configs[4] (t16_b4096, 512 commits per GPU per step).
 
 At 512 commits the configs[4] encode prep is 512 * 9 * 513 = 2.36 M jobs, past the 2^20 at which
-prep_launch (csrc/jindo.hip) takes the 12-wave prep256_kernel<2, true, 12>; smaller batches (every
+prep_launch (csrc/jindo_commit.hip) takes the 12-wave prep256_kernel<2, true, 12>; smaller batches (every
 other test) take the 4-wave form.  So these tests pin the kernels the jindo_commit /
 jindo_commit_2e16 lines actually run:
 

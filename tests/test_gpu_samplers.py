@@ -1,4 +1,4 @@
-"""GPU parity of the device samplers (csrc/csprng.hpp, jindo.hip section 6) against the C
+"""GPU parity of the device samplers (csrc/csprng.hpp, jindo_sample.hip) against the C
 restatement (oracle/oracle.c of_jindo_sample / of_uniform_words over OpenSSL AES), bit for bit:
 the AES-256-CTR UniformSampler stream, deltaInv, and every draw of Prover.Commit's randomness
 (lastRow, mask, encode noise with its deltaInv centres, MLWE noise) over several parameter sets,
