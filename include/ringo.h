@@ -589,6 +589,14 @@ rg_status rg_jindo_verify_dev(const rg_jindo* j, size_t batch, const uint64_t* d
 /* ------------------------------------------------------------------------------------ */
 /* Device memory helpers (so a cgo caller needs no HIP headers)                           */
 /* ------------------------------------------------------------------------------------ */
+/* rg_malloc: `bytes` of memory on the current device (RG_ERR_NOMEM when it has none left).
+ * rg_memcpy_*: asynchronous copies ordered on `stream` (NULL = the null stream) with the `_dev`
+ * calls issued on it, so a kernel launched after rg_memcpy_h2d on the same stream reads the
+ * copied data.  The host side may be ordinary pageable memory (a Go slice, malloc), and for such
+ * memory the call may return before the copy has happened: the caller may overwrite or free the
+ * source of rg_memcpy_h2d, and may read the destination of rg_memcpy_d2h, only after
+ * rg_stream_sync(stream) has returned.  rg_stream_sync returns when everything issued on `stream`
+ * so far has completed.  tools/abi_replay.c is a caller written to this contract. */
 rg_status rg_malloc(void** d_ptr, size_t bytes);
 rg_status rg_free(void* d_ptr);
 rg_status rg_memcpy_h2d(void* d_dst, const void* src, size_t bytes, void* stream);

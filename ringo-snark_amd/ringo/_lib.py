@@ -18,6 +18,11 @@ vp = ctypes.c_void_p
 
 _lib = None
 
+# include/ringo.h rg_status and RG_SAMPLER_LAYOUT (tests/test_capi_c.py holds them to the header)
+STATUS = {"RG_OK": 0, "RG_ERR_INVALID": -1, "RG_ERR_NOT_POW2": -2, "RG_ERR_UNSUPPORTED": -3, "RG_ERR_DEVICE": -4,
+          "RG_ERR_NOMEM": -5, "RG_ERR_RANK": -6}
+SAMPLER_LAYOUT = 2
+
 
 class RingoError(RuntimeError):
     """A libringo call failed.  `message` holds the reference's panic text where one exists
@@ -230,7 +235,8 @@ def check(status):
     if status != 0:
         L = lib()
         msg = L.rg_status_string(status).decode()
-        detail = L.rg_last_error().decode() if status in (-1, -3, -4) else ""
+        detail = L.rg_last_error().decode() if status in (STATUS["RG_ERR_INVALID"], STATUS["RG_ERR_UNSUPPORTED"],
+                                                             STATUS["RG_ERR_DEVICE"]) else ""
         raise RingoError(status, msg, detail)
     return status
 
