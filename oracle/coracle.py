@@ -46,6 +46,8 @@ def lib():
         L.of_jindo_sample.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                       ctypes.c_char_p, ctypes.c_uint64, ctypes.c_long, u64p, ctypes.c_long, u64p, u64p,
                                       i64p, i64p]
+        L.of_jindo_sample_census.argtypes = L.of_jindo_sample.argtypes + [ctypes.POINTER(OfCensus)]
+        L.of_census_size.restype = ctypes.c_size_t
         L.of_uniform_words.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_long,
                                        u64p]
         L.of_sampler_draws.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_double, ctypes.c_double, ctypes.c_long,
@@ -244,6 +246,14 @@ def make_params_struct(P, field_q, cls=OfJindoParams):
     return s
 
 
+class OfCensus(ctypes.Structure):
+    """oracle.c of_census: the paths of_jindo_sample's draws took"""
+    _fields_ = [(n, ctypes.c_int64) for n in ["cdt_draws", "cdt_tails", "cdt_tail_v0", "cdt_tail_v1"]] + [
+        ("cdt_min_rel", ctypes.c_double)] + [(n, ctypes.c_int64) for n in [
+            "cos_groups", "cos_max_base", "cos_max_rnd", "cos_over_base", "cos_over_rnd", "cos_zig_tail",
+            "cos_zig_wedge", "ml_zig_tail", "ml_zig_wedge", "cdt_enc_size", "cdt_mlwe_size"]]
+
+
 class CJindo:
     """C-oracle commit with injected randomness (same layouts as rg_jindo_commit)."""
 
@@ -288,9 +298,11 @@ class CJindo:
         lib().of_jindo_commit_core(ctypes.c_void_p(self.h), *[ptr(x) for x in a], ptr(o["incom"]), ptr(o["com"]))
         return o
 
-    def sample(self, sd, delta, seeds, first, v):
+    def sample(self, sd, delta, seeds, first, v, census=False):
         """The randomness of v.shape[0] commits (of_jindo_sample): sd = the six standard deviations
-        (ecd, ecd_blind, mask, mask_blind, mlwe, mask_mlwe), delta = deltaInv, seeds = 192 bytes."""
+        (ecd, ecd_blind, mask, mask_blind, mlwe, mask_mlwe), delta = deltaInv, seeds = 192 bytes.
+        census=True: returns (draws, census), the same draws and a dict of the oracle's path counts
+        (oracle.c of_census)."""
         s = self.ps
         B, nv = v.shape[0], v.shape[1]
         nm = s.in_msis + s.mlwe
@@ -301,12 +313,17 @@ class CJindo:
         sdv = (ctypes.c_double * 6)(*sd)
         dv = (ctypes.c_double * len(delta))(*delta)
         vv = np.ascontiguousarray(v, np.uint64)
-        rc = lib().of_jindo_sample(ctypes.c_void_p(self.h), sdv, dv, bytes(seeds), first, B, ptr(vv), nv,
-                                   ptr(o["last_row"]), ptr(o["mask"]), ptr(o["enc_noise"], i64p),
-                                   ptr(o["mlwe_noise"], i64p))
+        args = [ctypes.c_void_p(self.h), sdv, dv, bytes(seeds), first, B, ptr(vv), nv, ptr(o["last_row"]),
+                ptr(o["mask"]), ptr(o["enc_noise"], i64p), ptr(o["mlwe_noise"], i64p)]
+        cs = OfCensus()
+        if census:
+            assert lib().of_census_size() == ctypes.sizeof(OfCensus)
+            rc = lib().of_jindo_sample_census(*args, ctypes.byref(cs))
+        else:
+            rc = lib().of_jindo_sample(*args)
         if rc:
             raise RuntimeError("of_jindo_sample: libcrypto unavailable")
-        return o
+        return (o, {n: getattr(cs, n) for n, _ in OfCensus._fields_}) if census else o
 
     # ---- Prover.Evaluate core (prover.go:205-324), challenges injected ----
     def eval_shapes(self):

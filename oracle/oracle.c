@@ -1405,8 +1405,25 @@ static void cdt_init(of_cdt* C, double sigma) {
   C->tables = (uint64_t*)malloc(8 * (size_t)C->size * 128);
   for (int i = 0; i < 128; ++i) cdt_table((double)i / 128, sigma, C->tables + (size_t)i * C->size);
 }
-/* TwinCDTGaussianSampler.Sample (gaussian_twin_cdt.go:77-112) */
-static int64_t cdt_sample(const of_cdt* C, of_uni* U, double center) {
+/* Path census of of_jindo_sample (of_jindo_sample_census): which data-dependent branches the draws
+ * took.  Counting only: the draws are those of of_jindo_sample, byte for byte. */
+typedef struct {
+  int64_t cdt_draws;   /* TwinCDT encode draws */
+  int64_t cdt_tails;   /* ... with v0 != v1 (gaussian_twin_cdt.go:95-110) */
+  int64_t cdt_tail_v0; /* ... that returned v0 (p < cdf) */
+  int64_t cdt_tail_v1; /* ... that returned v1 */
+  double cdt_min_rel;  /* smallest |p - cdf| / cdf over the tails (HUGE_VAL: no tail with cdf > 0) */
+  int64_t cos_groups;  /* COSAC groups (an instance pair each) */
+  int64_t cos_max_base, cos_max_rnd;   /* most words one group drew from its base / rounded stream */
+  int64_t cos_over_base, cos_over_rnd; /* groups that drew more than 1024 words from it */
+  int64_t cos_zig_tail, cos_zig_wedge; /* COSAC's rounded sampler: normFloat tail entries (i == 0), wedge tests */
+  int64_t ml_zig_tail, ml_zig_wedge;   /* the MLWE mask column's roundedSampler likewise */
+  int64_t cdt_enc_size, cdt_mlwe_size; /* entries per TwinCDT table */
+} of_census;
+size_t of_census_size(void) { return sizeof(of_census); }
+
+/* TwinCDTGaussianSampler.Sample (gaussian_twin_cdt.go:77-112); cs: the encode draws' census or NULL */
+static int64_t cdt_sample(const of_cdt* C, of_uni* U, double center, of_census* cs) {
   double cFloor = floor(center), cFrac = center - cFloor;
   int64_t c0 = (int64_t)floor(128 * cFrac) % 128, c1 = (int64_t)ceil(128 * cFrac) % 128;
   uint64_t u = uni_sample(U);
@@ -1415,6 +1432,7 @@ static int64_t cdt_sample(const of_cdt* C, of_uni* U, double center) {
   if (f) v0 -= 1;
   int64_t v1 = bsearch_go(C->tables + c1 * C->size, C->size, u, &f);
   if (f) v1 -= 1;
+  if (cs) cs->cdt_draws++;
   if (v0 == v1) return v0 + (int64_t)cFloor + C->tail_lo;
   double cdf = 0, norm = sqrt(2 * M_PI) * C->sigma;
   for (int64_t x = C->tail_lo; x <= v0; x++) {
@@ -1422,6 +1440,11 @@ static int64_t cdt_sample(const of_cdt* C, of_uni* U, double center) {
     cdf += exp(-(xf - cFrac) * (xf - cFrac) / (2 * C->sigma * C->sigma)) / norm;
   }
   double p = (double)u / 18446744073709551616.0;
+  if (cs) {
+    cs->cdt_tails++;
+    if (p < cdf) cs->cdt_tail_v0++; else cs->cdt_tail_v1++;
+    if (cdf > 0 && fabs(p - cdf) / cdf < cs->cdt_min_rel) cs->cdt_min_rel = fabs(p - cdf) / cdf;
+  }
   if (p < cdf) return v0 + C->tail_lo + (int64_t)cFloor;
   return v1 + C->tail_lo + (int64_t)cFloor;
 }
@@ -1445,13 +1468,15 @@ static void zig_init(void) {
   zwn[0] = (v / znormal(RN)) / scale;
   zfn[0] = 0;
 }
-static double norm_float(of_uni* U) {
+/* zc: NULL, or the census counters {tail entries, wedge tests} of the calling sampler */
+static double norm_float(of_uni* U, int64_t* zc) {
   for (;;) {
     uint64_t r = uni_sample(U);
     uint64_t b = r >> 63, i = r % (1 << 7), j = (r >> 7) % (1ull << 52);
     double x = (double)(int64_t)((j ^ -b) + b) * zwn[i];
     if (j < zkn[i]) return x;
     if (i == 0) {
+      if (zc) zc[0]++;
       double u, v;
       for (;;) {
         u = -log(uni_float(U)) * (1.0 / RN);
@@ -1461,17 +1486,18 @@ static double norm_float(of_uni* U) {
       u += RN;
       return b == 1 ? -u : u;
     }
+    if (zc) zc[1]++;
     double f0 = zfn[i - 1], f1 = zfn[i];
     if (uni_float(U) * (f0 - f1) < exp(-0.5 * x * x) - f1) return x;
   }
 }
 /* COSACSampler.Sample (gaussian_cosac.go:22-57) */
-static int64_t cosac_sample(of_uni* base, of_uni* rnd, double center, double stdDev) {
+static int64_t cosac_sample(of_uni* base, of_uni* rnd, double center, double stdDev, int64_t* zc) {
   double cInt = round(center), cFrac = cInt - center;
   double r = uni_float(base);
   if (r < exp(-(cFrac * cFrac) / (2 * stdDev * stdDev)) / (sqrt(2 * M_PI) * stdDev)) return (int64_t)cInt;
   for (;;) {
-    double y = stdDev * norm_float(rnd);
+    double y = stdDev * norm_float(rnd, zc);
     uint64_t b = uni_sample(base) & 1;
     double yRound;
     int cmp;
@@ -1520,9 +1546,9 @@ static void set_random(const of_field* F, of_uni* U, uint64_t* z) {
 /* The randomness of `batch` commits (layouts: rg_jindo_sample_dev).  sd: ecd, ecd_blind, mask,
  * mask_blind, mlwe, mask_mlwe; delta: Encoder.deltaInv[exp]; seeds: 6 x 32 bytes in
  * rg_jindo_seeds order. */
-int of_jindo_sample(const of_jindo* J, const double* sd, const double* delta, const unsigned char* seeds,
-                    uint64_t first, long batch, const uint64_t* v, long nv, uint64_t* o_last, uint64_t* o_mask,
-                    int64_t* o_en, int64_t* o_mn) {
+static int jindo_sample(const of_jindo* J, const double* sd, const double* delta, const unsigned char* seeds,
+                        uint64_t first, long batch, const uint64_t* v, long nv, uint64_t* o_last, uint64_t* o_mask,
+                        int64_t* o_en, int64_t* o_mn, of_census* cen) {
   const of_jindo_params* P = &J->P;
   const int L = J->F.L, d = P->d, sl = P->slots, cs = P->cols * P->slots, nm = P->in_msis + P->mlwe;
   of_dom dom[6];
@@ -1532,6 +1558,12 @@ int of_jindo_sample(const of_jindo* J, const double* sd, const double* delta, co
   of_cdt ce, cm;
   cdt_init(&ce, sd[0]);
   cdt_init(&cm, sd[4]);
+  if (cen) {
+    memset(cen, 0, sizeof(*cen));
+    cen->cdt_min_rel = HUGE_VAL;
+    cen->cdt_enc_size = ce.size;
+    cen->cdt_mlwe_size = cm.size;
+  }
   uint64_t* digits = (uint64_t*)malloc(8 * (size_t)d);
   double* fp = (double*)malloc(8 * (size_t)d);
   uint64_t* first_row = (uint64_t*)calloc((size_t)cs * L, 8);
@@ -1588,14 +1620,22 @@ int of_jindo_sample(const of_jindo* J, const double* sd, const double* delta, co
         if (s == sd[0]) { /* twinCDT: the encode's instance, one word per sample */
           of_uni U;
           uni_init(&U, &dom[0], gpoly);
-          for (int k = 0; k < d; ++k) en[k] = cdt_sample(&ce, &U, -fp[k]);
+          for (int k = 0; k < d; ++k) en[k] = cdt_sample(&ce, &U, -fp[k], cen);
         } else { /* cosac: an instance pair per group of G consecutive samples, drawn in order */
           const int G = d < 8 ? d : 8;  /* the library's partition (jindo_sample.hip kCosGroup) */
           for (int g = 0; g < d / G; ++g) {
             of_uni B, R;
             uni_init(&B, &dom[1], gpoly * (uint64_t)(d / G) + (uint64_t)g);
             uni_init(&R, &dom[2], gpoly * (uint64_t)(d / G) + (uint64_t)g);
-            for (int k = g * G; k < (g + 1) * G; ++k) en[k] = cosac_sample(&B, &R, -fp[k], s);
+            for (int k = g * G; k < (g + 1) * G; ++k)
+              en[k] = cosac_sample(&B, &R, -fp[k], s, cen ? &cen->cos_zig_tail : NULL);
+            if (cen) {
+              cen->cos_groups++;
+              if ((int64_t)B.pos > cen->cos_max_base) cen->cos_max_base = (int64_t)B.pos;
+              if ((int64_t)R.pos > cen->cos_max_rnd) cen->cos_max_rnd = (int64_t)R.pos;
+              cen->cos_over_base += B.pos > 1024;
+              cen->cos_over_rnd += R.pos > 1024;
+            }
           }
         }
       }
@@ -1606,12 +1646,12 @@ int of_jindo_sample(const of_jindo* J, const double* sd, const double* delta, co
           for (int k = 0; k < d; ++k) {
             of_uni U;
             uni_init(&U, &dom[4], gpoly * d + k);
-            mn[k] = (int64_t)round(0 + norm_float(&U) * sd[5]);
+            mn[k] = (int64_t)round(0 + norm_float(&U, cen ? &cen->ml_zig_tail : NULL) * sd[5]);
           }
         } else {
           of_uni U;
           uni_init(&U, &dom[3], gpoly);
-          for (int k = 0; k < d; ++k) mn[k] = cdt_sample(&cm, &U, 0);
+          for (int k = 0; k < d; ++k) mn[k] = cdt_sample(&cm, &U, 0, NULL);
         }
       }
     }
@@ -1622,6 +1662,17 @@ int of_jindo_sample(const of_jindo* J, const double* sd, const double* delta, co
   free(fp);
   free(first_row);
   return 0;
+}
+int of_jindo_sample(const of_jindo* J, const double* sd, const double* delta, const unsigned char* seeds,
+                    uint64_t first, long batch, const uint64_t* v, long nv, uint64_t* o_last, uint64_t* o_mask,
+                    int64_t* o_en, int64_t* o_mn) {
+  return jindo_sample(J, sd, delta, seeds, first, batch, v, nv, o_last, o_mask, o_en, o_mn, NULL);
+}
+/* the same draws, and which paths they took */
+int of_jindo_sample_census(const of_jindo* J, const double* sd, const double* delta, const unsigned char* seeds,
+                           uint64_t first, long batch, const uint64_t* v, long nv, uint64_t* o_last,
+                           uint64_t* o_mask, int64_t* o_en, int64_t* o_mn, of_census* cs) {
+  return jindo_sample(J, sd, delta, seeds, first, batch, v, nv, o_last, o_mask, o_en, o_mn, cs);
 }
 
 /* n draws of one sampler (distribution tests): kind 0 TwinCDTGaussianSampler(sigma).Sample(center),
@@ -1642,9 +1693,9 @@ int of_sampler_draws(int kind, const unsigned char* seeds, double sigma, double 
       uni_init(&B, &d0, (uint64_t)(k / per_inst));
       uni_init(&R, &d1, (uint64_t)(k / per_inst));
     }
-    if (kind == 0) out[k] = cdt_sample(&C, &B, center);
-    else if (kind == 1) out[k] = cosac_sample(&B, &R, center, sigma);
-    else out[k] = (int64_t)round(center + norm_float(&B) * sigma);
+    if (kind == 0) out[k] = cdt_sample(&C, &B, center, NULL);
+    else if (kind == 1) out[k] = cosac_sample(&B, &R, center, sigma, NULL);
+    else out[k] = (int64_t)round(center + norm_float(&B, NULL) * sigma);
   }
   free(C.tables);
   return 0;

@@ -28,6 +28,8 @@ enum class Knob : int {
   JindoMac,    // RINGO_JINDO_MAC    l: mac_kernel instead of the MFMA MAC
   JindoSplit,  // RINGO_JINDO_SPLIT  0: commit_sampled on the caller's stream only
   JindoUniTries,  // RINGO_JINDO_UNI_TRIES n: uniform_whole_kernel gives up after n tries (tests the fix-up path)
+  JindoCdtPath,   // RINGO_JINDO_CDT_PATH exact: cdt2_noise_kernel's exact path for every sample; sum: and its
+                  //                      exact sum for every v0 != v1 tail (tests the paths draws never reach)
   Count
 };
 const char* knob(Knob k);

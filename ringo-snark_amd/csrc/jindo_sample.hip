@@ -51,10 +51,12 @@ struct SampleArgs {
   long long* mlwe_noise;  // [B][cols+1][nm][d]
   long long n_enc_pairs, n_ml_pairs;
   long long batch;
-  // cdt2_noise_kernel's tail bounds: [129][size + 2], row c, entry j + 1 = the reference's tail
-  // cdf sum_{x = tailLo}^{j} rho(x - c/128) / norm for j = -1 .. size (host, Go's order)
+  // cdt2_noise_kernel's tail bounds: [2][128][size + 2], lower then upper; row c, entry j + 1 bounds
+  // the reference's tail cdf sum_{x = tailLo}^{j} rho(x - cFrac) / norm, j = -1 .. size, over
+  // cFrac in [c, c + 1] / 128 (host, rg_jindo_set_stddevs)
   const double* cdt_sbound;
   const int* cdt_jmax;  // [128]: v0 <= jmax[c0] decides the sample as v0 (cdt2_noise_kernel)
+  double cdt_band;      // relative width of the band around the bounds that goes to the exact sum: 2^-40
   int* wq;              // [0] cdt2_noise_kernel's chunk counter, [2..3] cosac2's job counter (zeroed)
 };
 
@@ -89,7 +91,8 @@ __device__ __forceinline__ double enc_centre(const SampleArgs& a, const uint32_t
 // cdt_tail_kernel) are tools/experiments/legacy_samplers.patch.
 #pragma clang fp contract(off)
 constexpr int kCdtLdsMaxSize = 96;  // tables' high words + guide in LDS when size <= 96 (<= 145 KiB
-                                    // per workgroup with the 64 KiB AES table)
+                                    // per workgroup with the 64 KiB AES table; the waves' digit slots
+                                    // take the rest: cdt2_waves)
 constexpr int kCdtChunk = 8;        // consecutive polynomials per chunk (queue granularity; 32 / 16 / 8 A/B: profiles/r04q_queue_chunks_ab.txt)
 
 __device__ __forceinline__ double rl_f64(double x, int lane) {
@@ -138,11 +141,12 @@ __host__ __device__ constexpr int cdt_key_off(int size) { return cdt_guide_off(s
 //    gives the same lower bound unless u lies between the two tables' entries around it (two
 //    word compares; ~0.1% of samples search c1 in full);
 //  * a v0 != v1 tail compares p = u / 2^64 with the reference's cdf = sum_{x <= v0} rho(x - cFrac)
-//    / norm through bounds: that sum decreases with the centre, cFrac lies in [c0, c0 + 1] / 128,
-//    so S[c0 + 1][v0] (1 - 2^-40) <= cdf <= S[c0][v0] (1 + 2^-40) (S summed on the host in the same
-//    order; 2^-40 covers both libms and the float sums).  Outside that band the comparison is
-//    decided; inside it (p within 1e-12 of the sum: p ~ 1, unseen in practice) the wave sums the
-//    terms in the reference's order.  Results equal the reference's draw for draw.
+//    / norm through bounds: cFrac lies in [c0, c0 + 1] / 128, and the host bounds that sum over the
+//    interval from its values at the two ends (summed in the same order; rg_jindo_set_stddevs), so
+//    lo[c0][v0] (1 - 2^-40) <= cdf <= hi[c0][v0] (1 + 2^-40) (2^-40 covers both libms and the float
+//    sums).  Outside that band the comparison is decided; inside it (p ~ 1, unseen at NewParameters'
+//    widths; a few tails in a hundred at widths below 0.5) the wave sums the terms in the
+//    reference's order.  Results equal the reference's draw for draw.
 // deltaInv centres of coefficients 4 lane + h (encoder.go:153-165, Go's summation order) from the
 // polynomial's 256 digits in the wave's LDS slot dl: coefficient k reads digit (k + (i+1) slots)
 // mod 256, added when that index wrapped; fp = the negated centres.  Leading zero deltas (12 of 16
@@ -208,10 +212,21 @@ __global__ __launch_bounds__(64 * kCentreWaves) void cos_centre_kernel(SampleArg
   out[2 * lane + 1] = make_double2(-fp[2], -fp[3]);
 }
 
-constexpr int kCdt2Waves = 16;
+constexpr int kCdt2Waves = 16;  // per workgroup; fewer where the tables leave no room for 16 digit slots
+constexpr int kLdsBytes = 163840;
 __host__ __device__ constexpr int cdt2_dig_off(int size) { return cdt_key_off(size) + kKeyWords * 4; }
-__host__ __device__ constexpr int cdt2_jmax_off(int size) { return cdt2_dig_off(size) + kCdt2Waves * 1024; }
-__host__ __device__ constexpr int cdt2_dyn_lds(int size) { return cdt2_jmax_off(size) + 128 * 4; }
+__host__ __device__ constexpr int cdt2_jmax_off(int size, int waves) { return cdt2_dig_off(size) + waves * 1024; }
+__host__ __device__ constexpr int cdt2_dyn_lds(int size, int waves) { return cdt2_jmax_off(size, waves) + 128 * 4; }
+// the waves a workgroup runs at this table size: 16 up to 93 entries (NewParameters' tables have 89),
+// 15 at 95 (the kernel's layout follows blockDim)
+constexpr int cdt2_waves(int size) {
+  int w = kCdt2Waves;
+  while (w > 1 && cdt2_dyn_lds(size, w) + (int)sizeof(uint32_t) * kAesLds > kLdsBytes) --w;
+  return w;
+}
+static_assert(cdt2_waves(89) == kCdt2Waves && cdt2_waves(kCdtLdsMaxSize) >= 14 &&
+                  cdt2_dyn_lds(kCdtLdsMaxSize, cdt2_waves(kCdtLdsMaxSize)) + (int)sizeof(uint32_t) * kAesLds <= kLdsBytes,
+              "every accepted table fits beside the AES table");
 
 __global__ __launch_bounds__(64 * kCdt2Waves) void cdt2_noise_kernel(SampleArgs a) {
   __shared__ uint32_t lds[kAesLds];
@@ -223,7 +238,7 @@ __global__ __launch_bounds__(64 * kCdt2Waves) void cdt2_noise_kernel(SampleArgs 
   uint32_t* keyl = dyn + cdt_key_off(n) / 4;
   const int wl = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint4* dl = reinterpret_cast<uint4*>(reinterpret_cast<char*>(dyn) + cdt2_dig_off(n) + wl * 1024);
-  int* jmax = reinterpret_cast<int*>(reinterpret_cast<char*>(dyn) + cdt2_jmax_off(n));
+  int* jmax = reinterpret_cast<int*>(reinterpret_cast<char*>(dyn) + cdt2_jmax_off(n, (int)(blockDim.x >> 6)));
   aes_lds_fill(lds, a.te0);
   aes_key_fill(keyl, a.key[kDomEncCdt]);
   for (int i = threadIdx.x; i < 128 * n; i += blockDim.x) thi[i] = (uint32_t)(C.tables[i] >> 32);
@@ -280,7 +295,7 @@ __global__ __launch_bounds__(64 * kCdt2Waves) void cdt2_noise_kernel(SampleArgs 
       // top byte in table c0 holds <= 3 entries and none shares u's high word, so the lower bound
       // is lo + #(entries below u) with no equality (three LDS word compares); and v0 <= jmax[c0],
       // for which the reference returns v0 whatever v1 is: if v1 == v0 trivially, else because
-      // p = u / 2^64 <= t_c0[v0 + 1] / 2^64 < (1 - 2^-40) S[c0 + 1][v0] <= the cdf it compares
+      // p = u / 2^64 <= t_c0[v0 + 1] / 2^64 < (1 - 2^-40) lo[c0][v0] <= the cdf it compares
       // with (host-checked per table and index, rg_jindo_set_stddevs).  Other samples (a long
       // bucket, a high-word tie, an extreme v0) take the exact path below.
       int c0[4], v0[4];
@@ -324,8 +339,8 @@ __global__ __launch_bounds__(64 * kCdt2Waves) void cdt2_noise_kernel(SampleArgs 
             res[h] = (int64_t)w1 + C.tail_lo + (int64_t)flo[h];
             if (w0 != w1) {  // the tail: p < cdf -> v0's value (twin_cdt.go:95-110)
               const double p = __ull2double_rn(u[h]) / 18446744073709551616.0;
-              const double lo_b = a.cdt_sbound[(a0 + 1) * sstride + w0 + 1] * (1.0 - 9.094947017729282e-13);
-              const double hi_b = a.cdt_sbound[a0 * sstride + w0 + 1] * (1.0 + 9.094947017729282e-13);
+              const double lo_b = a.cdt_sbound[a0 * sstride + w0 + 1] * (1.0 - a.cdt_band);
+              const double hi_b = a.cdt_sbound[(128 + a0) * sstride + w0 + 1] * (1.0 + a.cdt_band);
               if (p < lo_b)
                 res[h] = (int64_t)w0 + C.tail_lo + (int64_t)flo[h];
               else if (!(p >= hi_b))
@@ -1030,8 +1045,7 @@ static rg_status sample_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, si
   }
   const rg_jindo_samplers& S = J->smp;
   // the shapes the device samplers cover (every NewParameters shape of a field with exp <= 64)
-  if (p.d != 256 || p.slots % 4 != 0 || S.cdt_enc_size > kCdtLdsMaxSize ||
-      cdt2_dyn_lds(S.cdt_enc_size) + (int)sizeof(uint32_t) * kAesLds > 163840) {
+  if (p.d != 256 || p.slots % 4 != 0 || S.cdt_enc_size > kCdtLdsMaxSize) {
     set_last_error("device sampling needs d = 256, slots % 4 == 0 and an encode TwinCDT table of <= 96 entries (got d = " +
                    std::to_string(p.d) + ", slots = " + std::to_string(p.slots) + ", table " +
                    std::to_string(S.cdt_enc_size) + ")");
@@ -1078,9 +1092,14 @@ static rg_status sample_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, si
   a.batch = (long long)batch;
   {
     const long long npoly = (long long)batch * (p.cols + 1) * p.rows;
-    const unsigned g = (unsigned)std::min<long long>((npoly + kCdt2Waves - 1) / kCdt2Waves, 256);
+    const int cw = cdt2_waves(S.cdt_enc_size);
+    const unsigned g = (unsigned)std::min<long long>((npoly + cw - 1) / cw, 256);
     a.cdt_sbound = S.cdt_sbound.as<double>();
     a.cdt_jmax = S.cdt_jmax.as<int>();
+    // experiments build, RINGO_JINDO_CDT_PATH=sum: an infinite band, so neither bound decides (the
+    // products are +-inf, or NaN at a zero sum) and every tail goes through the exact sum
+    const char* kp = knob(Knob::JindoCdtPath);
+    a.cdt_band = kp && !strcmp(kp, "sum") ? HUGE_VAL : 9.094947017729282e-13;
     a.wq = sc->wq.as<int>();
     RG_HIP(hipMemsetAsync(a.wq, 0, 4 * sizeof(int), st));  // [0]: cdt2's chunks, [2..3]: cosac2's jobs (u64)
     // the COSAC centres (small) ahead of cdt2 on st: launched on s_cos beside cdt2 they wait for
@@ -1093,7 +1112,7 @@ static rg_status sample_stage(rg_jindo* J, size_t batch, const uint64_t* d_v, si
       RG_HIP(hipEventRecord(e_dig, st));
       RG_HIP(hipStreamWaitEvent(s_cos, e_dig, 0));
     }
-    hipLaunchKernelGGL(cdt2_noise_kernel, dim3(g), dim3(64 * kCdt2Waves), cdt2_dyn_lds(S.cdt_enc_size), st, a);
+    hipLaunchKernelGGL(cdt2_noise_kernel, dim3(g), dim3(64 * cw), cdt2_dyn_lds(S.cdt_enc_size, cw), st, a);
     RG_TRY(check_launch("jindo enc noise (TwinCDT)"));
     const long long w2 = kCos2Threads / 64;
     const unsigned g2 = (unsigned)std::min<long long>((ncos + w2 - 1) / w2, 256);
@@ -1189,21 +1208,42 @@ rg_status rg_jindo_set_stddevs(rg_jindo* J, const rg_jindo_stddevs* sd) {
         sb[(size_t)c * (n + 2) + j + 1] = cdf;
       }
     }
-    RG_TRY(S.cdt_sbound.upload(sb.data(), sb.size() * 8));
+    // Bounds of that sum f_j over cFrac in [c, c + 1] / 128 from its values at the two ends.  f_j
+    // falls with the centre while the terms left of it dominate (every j at NewParameters' widths,
+    // where f_j tracks the normal cdf), but not in general: at small widths the lattice sum itself
+    // swings with the centre (sum_x rho(x - c) / norm ~ 1 + 2 exp(-2 pi^2 sigma^2) cos(2 pi c)), and
+    // terms right of the centre rise with it.  So: min and max of the two ends, widened by the
+    // chord's error h^2 / 8 max |f_j''|, h = 1/128, with |f_j''| <= sum_x |z^2 - 1| rho / (norm sigma^2)
+    // (z = (x - c) / sigma) <= (2 + 1.14 / sigma) / sigma^2: (z^2 + 1) exp(-z^2 / 2) has integral
+    // 2 sqrt(2 pi) and total variation < 2.85, which bounds its lattice sum.  7e-7 at ecdStdDev = 4.79.
+    // (tests/test_oracle_sampler_paths.py checks the claim on a grid of centres.)  The lower bound is
+    // clamped at 0: the cdf is not negative, and a negative bound times cdt_band's (1 - inf) would be +inf.
+    const double chord = (2.0 + 1.14 / sigma) / (sigma * sigma) / (8.0 * 128.0 * 128.0);
+    std::vector<double> lohi((size_t)2 * 128 * (n + 2));
+    for (int c = 0; c < 128; ++c)
+      for (int k = 0; k < n + 2; ++k) {
+        const double s0 = sb[(size_t)c * (n + 2) + k], s1 = sb[(size_t)(c + 1) * (n + 2) + k];
+        lohi[(size_t)c * (n + 2) + k] = std::max(0.0, std::min(s0, s1) - chord);
+        lohi[(size_t)(128 + c) * (n + 2) + k] = std::max(s0, s1) + chord;
+      }
+    RG_TRY(S.cdt_sbound.upload(lohi.data(), lohi.size() * 8));
     // jmax[c]: the largest J with, for every v0 = j in [-1, J] of table c, the bound on p
     // (t_c[j + 1] / 2^64, or 1 past the table) below the smallest cdf the reference can compare it
-    // with (S[c + 1][j] (1 - 2^-40)), again shrunk by 2^-40 for the double rounding of p
+    // with (the lower bound (1 - 2^-40)), again shrunk by 2^-40 for the double rounding of p
     std::vector<int> jm(128);
     for (int c = 0; c < 128; ++c) {
       const uint64_t* t = enc.data() + (size_t)c * n;
       int J = -2;
       for (int j = -1; j <= n; ++j) {
         const double pu = (j + 1 < n ? (double)t[j + 1] / 18446744073709551616.0 : 1.0) * (1.0 + 9.094947017729282e-13);
-        if (!(pu < sb[(size_t)(c + 1) * (n + 2) + j + 1] * (1.0 - 9.094947017729282e-13))) break;
+        if (!(pu < lohi[(size_t)c * (n + 2) + j + 1] * (1.0 - 9.094947017729282e-13))) break;
         J = j;
       }
       jm[c] = J;
     }
+    // experiments build, RINGO_JINDO_CDT_PATH=exact | sum: no sample takes the guide-table fast path
+    if (const char* kp = knob(Knob::JindoCdtPath); kp && (!strcmp(kp, "exact") || !strcmp(kp, "sum")))
+      std::fill(jm.begin(), jm.end(), -2);
     RG_TRY(S.cdt_jmax.upload(jm.data(), jm.size() * 4));
   }
   RG_TRY(S.cdt_mlwe.upload(ml.data(), ml.size() * 8));

@@ -64,6 +64,30 @@ def test_uniform_long_draws_fixup(tmp_path, tries):
     assert (got["mask"].view(np.uint64) == want["mask"]).all()
 
 
+@pytest.mark.parametrize("case", ["small_ecd_0.2", "v_qm1"])
+@pytest.mark.parametrize("path", ["exact", "sum"])
+def test_cdt_forced_paths(tmp_path, path, case):
+    """cdt2_noise_kernel's paths that draws never choose, forced on the experiments build
+    (RINGO_JINDO_CDT_PATH, tests/exp_child.py): `exact` sends every sample down the exact path
+    (both table searches) instead of the guide-table fast path; `sum` also sends every v0 != v1 tail
+    through the exact sum across the wave, which otherwise needs p within 2^-40 of the cdf.  On the
+    small-ecd case (both tail outcomes occur: the census) and one at the reference's widths,
+    enc_noise still equals the oracle's."""
+    import subprocess
+    import sys
+
+    from tests import sampler_path_cases as spc
+    want, census = spc.oracle_draws(case)
+    if case == "small_ecd_0.2":  # the sum decides in both directions
+        assert census["cdt_tail_v0"] >= 30 and census["cdt_tail_v1"] >= 30
+    assert census["cdt_tails"] > 0
+    out = tmp_path / f"cdt_{path}.npz"
+    r = subprocess.run([sys.executable, os.path.join(HERE, "exp_child.py"), "cdt", path, str(out), case],
+                       capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert (np.load(out)["enc_noise"] == want["enc_noise"]).all()
+
+
 @pytest.mark.parametrize("name", ["t10_b1", "mult_t8193_b12"])
 def test_delta_inv_matches_bigfloat(name):
     P = PARAMS[name]
