@@ -299,6 +299,65 @@ rg_status rg_buckler_lin_check(const rg_lincheck* lc, const uint64_t* batch_cons
                                const uint64_t* mask, const uint64_t* w, size_t n_w, size_t jindo_rank, uint64_t* quo,
                                uint64_t* rem_lo, uint64_t* rem_hi);
 
+/* ---- Buckler verifier's checks (buckler/verifier.go:178-315) ------------------------------ */
+/* What Verifier.Verify computes after the transcript: pwEvals, vanishEval, arithCheck, linCheck and
+ * sumCheck, decided on the device.  One call enqueues the whole decision on `stream` -- the power
+ * vector of linCheckConst, every checker's transpose of it, ONE batched cyclic InvNTT at the witness
+ * rank over those and the public witnesses (Encode; the zeros EncodeTo writes above `rank` add
+ * nothing to Evaluate, so the embedding rank never appears), ONE batched Evaluate at evalPoint and
+ * ONE one-workgroup kernel with all the scalar algebra -- and leaves one verdict word; nothing is
+ * copied back and nothing is waited for inside.  Everything is Montgomery, canonical and injected.
+ * The rest of Verify stays where it is: the transcript with the caller, polyVerifier.Verify =
+ * rg_jindo_verify_dev (before or after), the public witnesses pwBase / pwMask on the host, the
+ * projection matrix by rg_buckler_checker_set_xof* on the shared checker before the call.
+ *
+ * The handle holds what Compile fixes.  enc_plan: the encoder's cyclic plan at the witness rank (a
+ * negacyclic plan is RG_ERR_INVALID).  lin / arith / sum: HasLinearCheck / HasArithmeticCheck /
+ * HasSumCheck; each may be NULL, all three NULL is RG_ERR_INVALID.  Handles are borrowed and outlive
+ * the verifier.  RG_ERR_INVALID also for: a `lin` whose encoder plan has another rank or field, a
+ * circuit of another field, a circuit or pair index >= w_cnt (the reference indexes pf.Evals with
+ * witness IDs < wCnt), a public-witness index >= n_pw, jindo_rank < rank - 1.  RG_ERR_UNSUPPORTED for
+ * a limb count other than 1, 2, 4, 7, 14.  rg_last_error has the reason.  Creating a verifier
+ * touches no device.
+ *
+ * pf.Evals is laid out as verifier.go:120-214 walks roundComIdx: w_cnt witnesses, the lin mask (if
+ * lin), the sum mask (if sum), the arith quo (if arith), lin quo / remLo / remHi, sum quo / remLo /
+ * remHi; rg_buckler_verifier_n_evals is its length.
+ *
+ * d_evals [n_evals][L]; d_pw [n_pw][rank][L], the public-witness vectors (NULL iff n_pw = 0);
+ * d_chal [5][L]: evalPoint, arithBatchConst, linCheckBatchConst, linCheckConst, sumCheckBatchConst;
+ * d_mask_sums [2][L]: LinCheckMaskSum, SumCheckMaskSum (those of absent checks are ignored; NULL is
+ * allowed with arith alone); d_verdict: one word, 0 iff the reference's three checks all return true
+ * -- the reference returns at the first failure, the device reports every one (bits below; a check
+ * the handle lacks never sets its bits).  Optional d_sides [8][L]: arith (eval, test), lin (shift *
+ * remLo, eval, test), sum (shift * remLo, eval, test), zeros for absent checks.  Optional d_pw_evals
+ * [n_pw][L].  d_scratch holds rg_buckler_verify_checks_scratch_bytes(v) bytes; calls on different
+ * streams use different scratch.  Every argument is validated before the device is touched
+ * (RG_ERR_INVALID); no buffer may alias another.  The form without `_dev` takes host pointers and is
+ * synchronous.
+ *
+ * The reference is mirrored where it is odd: ctx.sumCheckSums is not read by the verifier's sumCheck
+ * (verifier.go:296-315), and evalCircuit multiplies every constraint by the same batchConst, not by
+ * its powers (verifier.go:235). */
+#define RG_BK_VERIFY_ARITH 1    /* arithCheck: eval != quoEval * vanishEval */
+#define RG_BK_VERIFY_LIN_REM 2  /* linCheck: remHiEval != evalPoint^(jindoRank - (rank - 1)) * remLoEval */
+#define RG_BK_VERIFY_LIN 4      /* linCheck: the main identity fails */
+#define RG_BK_VERIFY_SUM_REM 8  /* sumCheck: the remHi identity fails */
+#define RG_BK_VERIFY_SUM 16     /* sumCheck: the main identity fails */
+typedef struct rg_bverifier rg_bverifier;
+rg_status rg_buckler_verifier_create(const rg_ntt* enc_plan, size_t jindo_rank, size_t w_cnt, size_t n_pw,
+                                     const rg_lincheck* lin, const rg_circuit* arith, const rg_circuit* sum,
+                                     rg_bverifier** out);
+void rg_buckler_verifier_destroy(rg_bverifier* v);
+size_t rg_buckler_verifier_n_evals(const rg_bverifier* v);
+size_t rg_buckler_verify_checks_scratch_bytes(const rg_bverifier* v);
+rg_status rg_buckler_verify_checks_dev(const rg_bverifier* v, const uint64_t* d_evals, const uint64_t* d_pw,
+                                       const uint64_t* d_chal, const uint64_t* d_mask_sums, uint64_t* d_verdict,
+                                       uint64_t* d_sides, uint64_t* d_pw_evals, uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_verify_checks(const rg_bverifier* v, const uint64_t* evals, const uint64_t* pw,
+                                   const uint64_t* chal, const uint64_t* mask_sums, uint64_t* verdict,
+                                   uint64_t* sides, uint64_t* pw_evals);
+
 /* ---- Buckler norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---- */
 /* decomposeBig on the device: a Montgomery element w is taken out of Montgomery form, centred
  * (x > q >> 1 stands for x - q) and walked down the base b_0, b_1, ...: digit +1 and x -= b_j while

@@ -16,18 +16,10 @@
 #include <cstring>
 #include <vector>
 
+#include "buckler_impl.hpp"
 #include "common.hpp"
 #include "field.hpp"
 #include "ntt_plan.hpp"
-
-struct rg_circuit {
-  rg_field f;
-  int nc = 0;        // constraints
-  long long nt = 0;  // terms
-  long long max_w = -1, max_pw = -1;
-  rg::DevBuf prog;   // term_off [nc+1] u32 | pw [nt] i32 | wit_off [nt+1] u32 | wit [nwit] u32 | coeffs [nt][L] u64
-  size_t off_pw = 0, off_wo = 0, off_wi = 0, off_cf = 0;  // byte offsets into prog
-};
 
 namespace rg {
 

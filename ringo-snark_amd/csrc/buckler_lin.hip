@@ -19,38 +19,11 @@
 #include <cstring>
 #include <vector>
 
+#include "buckler_impl.hpp"
 #include "common.hpp"
 #include "field.hpp"
 #include "host_field.hpp"
 #include "ntt_plan.hpp"
-
-enum { RG_CHK_NTT = 0, RG_CHK_AUT = 1, RG_CHK_PROJ = 2, RG_CHK_RECOMPOSE = 3 };
-
-struct rg_linchecker {
-  int kind = 0;
-  rg_field f;
-  long long rank = 0;
-  rg_ntt* ntt = nullptr;  // NTT: the negacyclic plan (owned)
-  uint64_t scale[16];     //      SetUint64(rank)
-  long long idx = 0, idx_inv = 0;  // aut
-  int ntt_domain = 0;
-  rg::DevBuf bits;  // proj: [rank][4] u32, bit i of column j set <=> proj[i][j] (allocated by set_xof)
-  bool bits_set = false;
-  long long nb = 0;  // recompose
-  rg::DevBuf base;   //            [nb][L]
-  ~rg_linchecker() {
-    if (ntt) rg_ntt_destroy(ntt);
-  }
-};
-
-struct rg_lincheck {
-  const rg_ntt* enc = nullptr;  // cyclic at rank (borrowed)
-  const rg_ntt* emb = nullptr;  // cyclic at emb (borrowed)
-  std::vector<const rg_linchecker*> chk;
-  int n_pairs = 0;
-  long long max_w = -1;
-  rg::DevBuf prog;  // pair_off [n_chk+1] u32 | pairs [n_pairs][2] u32 (wOut, wIn)
-};
 
 namespace rg {
 

@@ -133,6 +133,13 @@ _SIGS = {
                                                 vp]),
     "rg_buckler_lin_check": (ctypes.c_int, [vp, u64p, u64p, u64p, u64p, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p,
                                             u64p]),
+    "rg_buckler_verifier_create": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp,
+                                                  ctypes.POINTER(vp)]),
+    "rg_buckler_verifier_destroy": (None, [vp]),
+    "rg_buckler_verifier_n_evals": (ctypes.c_size_t, [vp]),
+    "rg_buckler_verify_checks_scratch_bytes": (ctypes.c_size_t, [vp]),
+    "rg_buckler_verify_checks_dev": (ctypes.c_int, [vp] * 10),
+    "rg_buckler_verify_checks": (ctypes.c_int, [vp] + [u64p] * 7),
     "rg_buckler_dcmp_create": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.POINTER(vp)]),
     "rg_buckler_dcmp_destroy": (None, [vp]),
     "rg_buckler_dcmp_inf_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),

@@ -495,6 +495,85 @@ def ArithCheck(field, rank, embRank, arithCheckMaxRank, batchConst, constraints,
                    False)
 
 
+# ---- the verifier's checks (buckler/verifier.go:178-315) -------------------------------------------
+# verdict bits of rg_buckler_verify_checks* (include/ringo.h RG_BK_VERIFY_*)
+VERIFY_ARITH, VERIFY_LIN_REM, VERIFY_LIN, VERIFY_SUM_REM, VERIFY_SUM = 1, 2, 4, 8, 16
+
+
+class VerifyPlan:
+    """What Verifier.Verify's checks take from the compiled context (rg_bverifier): the encoder's
+    plan at `rank`, jindoRank, wCnt, the number of public witnesses, and the linear check (a
+    LinCheckPlan), the arithmetic and the sum-check constraints (Circuit objects or constraint
+    lists), each optional.  `n_evals` is the length of pf.Evals in the reference's order: wCnt
+    witnesses, lin mask, sum mask, arith quo, lin quo / remLo / remHi, sum quo / remLo / remHi."""
+
+    def __init__(self, field, rank, jindoRank, wCnt, nPw, lin=None, arith=None, sum=None, enc=None):
+        self.field, self.rank, self.jindoRank, self.wCnt, self.nPw = field, rank, jindoRank, wCnt, nPw
+        self.enc = enc if enc is not None else (lin.enc if lin is not None else NewCyclicTransformer(field, rank))
+        as_circ = lambda c: c if c is None or isinstance(c, Circuit) else Circuit(field, c)  # noqa: E731
+        self.lin, self.arith, self.sum = lin, as_circ(arith), as_circ(sum)  # kept alive: the handle borrows them
+        h = vp()
+        _status(lib().rg_buckler_verifier_create(self.enc.h, jindoRank, wCnt, nPw, lin.h if lin is not None else None,
+                                                 self.arith.h if self.arith is not None else None,
+                                                 self.sum.h if self.sum is not None else None, ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+        self.n_evals = lib().rg_buckler_verifier_n_evals(h)
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_buckler_verifier_destroy(self.h)
+            self.h = None
+
+    def scratch_bytes(self):
+        return lib().rg_buckler_verify_checks_scratch_bytes(self.h)
+
+    def checks_dev(self, d_evals, d_pw, d_chal, d_mask_sums, d_verdict, d_sides=None, d_pw_evals=None, d_scratch=None,
+                   stream=None):
+        """rg_buckler_verify_checks_dev: d_evals [n_evals][L], d_pw [nPw][rank][L] (None iff nPw = 0),
+        d_chal [5][L] (evalPoint, arithBatchConst, linCheckBatchConst, linCheckConst,
+        sumCheckBatchConst), d_mask_sums [2][L], d_verdict one word; optional d_sides [8][L] and
+        d_pw_evals [nPw][L].  Asynchronous on `stream`."""
+        L = self.field.L
+        opt = lambda t, n: _addr(t, n) if t is not None else None  # noqa: E731
+        _status(lib().rg_buckler_verify_checks_dev(
+            self.h, _addr(d_evals, self.n_evals * L), opt(d_pw, self.nPw * self.rank * L), _addr(d_chal, 5 * L),
+            opt(d_mask_sums, 2 * L), _addr(d_verdict, 1), opt(d_sides, 8 * L), opt(d_pw_evals, self.nPw * L),
+            opt(d_scratch, self.scratch_bytes() // 8), _stream(stream)))
+
+    def checks(self, evals, pw, chal, maskSums):
+        """rg_buckler_verify_checks (host arrays, synchronous) -> (verdict, sides [8][L], pwEvals [nPw][L])."""
+        L = self.field.L
+        arr = lambda a, n: None if a is None else np.ascontiguousarray(np.asarray(a, np.uint64).reshape(n, L))  # noqa: E731
+        ev, ch, ms = arr(evals, self.n_evals), arr(chal, 5), arr(maskSums, 2)
+        pwa = None if self.nPw == 0 else np.ascontiguousarray(np.asarray(pw, np.uint64).reshape(self.nPw, self.rank, L))
+        verdict = np.full(1, 2 ** 64 - 1, np.uint64)
+        sides = np.full((8, L), 2 ** 64 - 1, np.uint64)
+        pwe = np.full((max(self.nPw, 1), L), 2 ** 64 - 1, np.uint64)
+        _status(lib().rg_buckler_verify_checks(self.h, ptr(ev), ptr(pwa), ptr(ch), ptr(ms), ptr(verdict), ptr(sides),
+                                               ptr(pwe)))
+        return int(verdict[0]), sides, pwe[:self.nPw]
+
+
+def VerifyChecks(field, rank, jindoRank, wCnt, challenges, maskSums, evals, pw, checkers, linConstraints,
+                 arithConstraints, sumConstraints):
+    """Verifier.Verify after the transcript and polyVerifier.Verify (verifier.go:178-216): returns
+    (verdict, sides, pwEvals); verdict 0 <=> arithCheck, linCheck and sumCheck all return true.
+    challenges [5][L] = evalPoint, arithBatchConst, linCheckBatchConst, linCheckConst,
+    sumCheckBatchConst; maskSums [2][L] = LinCheckMaskSum, SumCheckMaskSum; evals = pf.Evals; pw =
+    the public-witness vectors [nPw][rank][L] (None without any).  A check whose constraints are
+    None is absent (HasLinearCheck / HasArithmeticCheck / HasSumCheck false)."""
+    lin = None
+    if linConstraints is not None:  # the embedding rank plays no part in the verifier's checks
+        lin = linConstraints if isinstance(linConstraints, LinCheckPlan) else LinCheckPlan(field, rank, rank, checkers,
+                                                                                           linConstraints)
+    nPw = 0 if pw is None else len(pw)
+    plan = VerifyPlan(field, rank, jindoRank, wCnt, nPw, lin, arithConstraints, sumConstraints)
+    if np.asarray(evals).reshape(-1, field.L).shape[0] < plan.n_evals:
+        raise RingoPanic("index out of range")  # pf.Evals[roundComIdx]
+    return plan.checks(np.asarray(evals, np.uint64).reshape(-1, field.L)[:plan.n_evals], pw, challenges, maskSums)
+
+
 # ---- norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---------------
 def decomposeBig(x, base, q):
     """decomposeBig (utils.go:34-56) on Python ints: x in [0, q) -> len(base) digits in {-1, 0, 1}."""

@@ -13,6 +13,7 @@
  *   abi_replay bigpoly DIR       INTEGRATION.md section 1
  *   abi_replay jindo DIR         INTEGRATION.md section 2 (Commit, Evaluate, Verify, sampled Commit)
  *   abi_replay buckler DIR       INTEGRATION.md section 3 (linear check, decomposition, encode)
+ *   abi_replay bverify DIR       INTEGRATION.md section 3, Verifier.Verify's checks (one verdict word)
  *
  * Exit status: 0; 2 when a call returned a status other than the expected one (the call,
  * rg_status_string and rg_last_error go to stderr); 3 for a usage or file error.
@@ -273,6 +274,13 @@ static int mode_layout(void) {
     printf("%d %s\n", st_, #call);            \
   } while (0)
 
+/* the same without the line of output */
+#define QUIET(want, call)                     \
+  do {                                        \
+    int st_ = (int)(call);                    \
+    if (st_ != (want)) fail(#call, st_, want); \
+  } while (0)
+
 static int mode_refuse(void) {
   const uint64_t q63[1] = {UINT64_C(0x4452100000000001)}; /* 47104^4 + 1 */
   const uint64_t even[1] = {4};
@@ -293,6 +301,19 @@ static int mode_refuse(void) {
   EXPECT(RG_ERR_INVALID, rg_set_probe(1)); /* the product library has no measurement switch */
   EXPECT(RG_OK, rg_set_probe(0));
   if (rg_jindo_scratch_bytes(NULL, 3) != 0) fail("rg_jindo_scratch_bytes(NULL, 3) != 0", 1, 0);
+  /* the Buckler verifier's entries: checked, not printed (the lines above are read as a fixed set) */
+  {
+    rg_bverifier* v = NULL;
+    uint64_t word[1] = {0};
+    QUIET(RG_ERR_INVALID, rg_buckler_verifier_create(NULL, 128, 4, 0, NULL, NULL, NULL, &v));
+    QUIET(RG_ERR_INVALID, rg_buckler_verifier_create(NULL, 128, 4, 0, NULL, NULL, NULL, NULL));
+    QUIET(RG_ERR_INVALID, rg_buckler_verify_checks_dev(NULL, one, NULL, one, one, word, NULL, NULL, out, NULL));
+    QUIET(RG_ERR_INVALID, rg_buckler_verify_checks(NULL, one, NULL, one, one, word, NULL, NULL));
+    if (v != NULL) fail("rg_buckler_verifier_create left a handle behind", 1, 0);
+    if (rg_buckler_verifier_n_evals(NULL) != 0) fail("rg_buckler_verifier_n_evals(NULL) != 0", 1, 0);
+    if (rg_buckler_verify_checks_scratch_bytes(NULL) != 0) fail("rg_buckler_verify_checks_scratch_bytes(NULL) != 0", 1, 0);
+    rg_buckler_verifier_destroy(NULL);
+  }
   rg_field_destroy(f);
   return 0;
 }
@@ -626,6 +647,113 @@ static int mode_buckler(void) {
   return 0;
 }
 
+/* ---- Verifier.Verify's checks --------------------------------------- */
+/* One constraint list as rg_buckler_circuit_create takes it: PREFIX_term_off [nc + 1], PREFIX_coeffs
+ * [nt][L], PREFIX_pw_idx [nt] (int64, < 0: none), PREFIX_wit_off [nt + 1], PREFIX_wit [nwit]. */
+static rg_circuit* circuit_from_files(const rg_field* f, const char* prefix, size_t e) {
+  char key[64], name[64];
+  snprintf(key, sizeof key, "%s_nc", prefix);
+  const size_t nc = kv(key);
+  snprintf(key, sizeof key, "%s_nt", prefix);
+  const size_t nt = kv(key);
+  snprintf(key, sizeof key, "%s_nwit", prefix);
+  const size_t nwit = kv(key);
+  snprintf(name, sizeof name, "%s_term_off", prefix);
+  uint64_t* to64 = read_bin(name, (nc + 1) * 8);
+  snprintf(name, sizeof name, "%s_coeffs", prefix);
+  uint64_t* coeffs = read_bin(name, nt * e);
+  snprintf(name, sizeof name, "%s_pw_idx", prefix);
+  long long* pw_idx = read_bin(name, nt * 8);
+  snprintf(name, sizeof name, "%s_wit_off", prefix);
+  uint64_t* wo64 = read_bin(name, (nt + 1) * 8);
+  snprintf(name, sizeof name, "%s_wit", prefix);
+  uint64_t* wit = read_bin(name, nwit * 8);
+  size_t* term_off = xmalloc((nc + 1) * sizeof *term_off);
+  size_t* wit_off = xmalloc((nt + 1) * sizeof *wit_off);
+  for (size_t i = 0; i <= nc; i++) term_off[i] = (size_t)to64[i];
+  for (size_t i = 0; i <= nt; i++) wit_off[i] = (size_t)wo64[i];
+  rg_circuit* c = NULL;
+  CK(rg_buckler_circuit_create(f, nc, term_off, coeffs, pw_idx, wit_off, wit, &c));
+  free(to64), free(coeffs), free(pw_idx), free(wo64), free(wit), free(term_off), free(wit_off);
+  return c;
+}
+
+static int mode_bverify(void) {
+  kv_load();
+  const int L = (int)kv("limbs");
+  const size_t rank = kv("rank"), jindo_rank = kv("jindo_rank"), w_cnt = kv("w_cnt"), n_pw = kv("n_pw");
+  const size_t nb = kv("recompose_nb"), n_pairs = kv("n_pairs"), ncases = kv("ncases");
+  const long long aut_idx = (long long)kv("aut_idx");
+  const size_t e = (size_t)L * 8;
+  enum { N_CHK = 4 };
+
+  /* what Compile fixes: the encoder's plan, the checkers, the three constraint sets */
+  uint64_t* q = read_bin("q", e);
+  rg_field* f = NULL;
+  CK(rg_field_create(L, q, &f));
+  rg_ntt* enc_plan = NULL;
+  CK(rg_ntt_create(f, (int)rank, 0, &enc_plan));
+  rg_linchecker* chk[N_CHK] = {NULL, NULL, NULL, NULL};
+  uint64_t* rbase = read_bin("recompose_base", nb * e);
+  uint8_t* xof = read_bin("xof", rank * 32);
+  CK(rg_buckler_checker_create_ntt(f, rank, &chk[0]));
+  CK(rg_buckler_checker_create_aut(f, rank, aut_idx, 0, &chk[1]));
+  CK(rg_buckler_checker_create_proj(f, rank, &chk[2]));
+  CK(rg_buckler_checker_create_recompose(f, rank, rbase, nb, &chk[3]));
+  uint64_t* off64 = read_bin("pair_off", (N_CHK + 1) * 8);
+  size_t pair_off[N_CHK + 1];
+  for (int i = 0; i <= N_CHK; i++) pair_off[i] = (size_t)off64[i];
+  uint64_t* pairs = read_bin("pairs", n_pairs * 2 * 8);
+  const rg_linchecker* const chks[N_CHK] = {chk[0], chk[1], chk[2], chk[3]};
+  rg_lincheck* lc = NULL; /* the verifier never reads the embedding plan: the encoder's stands in */
+  CK(rg_buckler_lincheck_create(enc_plan, enc_plan, N_CHK, chks, pair_off, pairs, &lc));
+  rg_circuit *arith = circuit_from_files(f, "arith", e), *sum = circuit_from_files(f, "sum", e);
+  rg_bverifier* v = NULL;
+  CK(rg_buckler_verifier_create(enc_plan, jindo_rank, w_cnt, n_pw, lc, arith, sum, &v));
+  const size_t n_evals = rg_buckler_verifier_n_evals(v);
+  const uint64_t info[2] = {(uint64_t)n_evals, (uint64_t)rg_buckler_verify_checks_scratch_bytes(v)};
+  write_bin("info", info, sizeof info);
+
+  /* per proof: the projection matrix from the transcript's XOF bytes, then one call and one word */
+  CK(rg_buckler_checker_set_xof(chk[2], xof));
+  uint64_t* d_pw = dput_file("pw", n_pw * rank * e);
+  uint64_t* d_scr = dalloc(rg_buckler_verify_checks_scratch_bytes(v));
+  for (size_t i = 0; i < ncases; i++) {
+    uint64_t* d_evals = dput_file(idx("evals", i), n_evals * e);
+    uint64_t *d_chal = dput_file(idx("chal", i), 5 * e), *d_ms = dput_file(idx("mask_sums", i), 2 * e);
+    uint64_t *d_verdict = dout(8), *d_sides = dout(8 * e), *d_pwe = dout(n_pw * e);
+    CK(rg_buckler_verify_checks_dev(v, d_evals, d_pw, d_chal, d_ms, d_verdict, d_sides, d_pwe, d_scr, NULL));
+    uint64_t verdict = 0;
+    d2h(&verdict, d_verdict, 8); /* the one word */
+    printf("case %zu verdict %" PRIu64 "\n", i, verdict);
+    write_bin(idx("verdict", i), &verdict, 8);
+    dsave(idx("sides", i), d_sides, 8 * e);
+    dsave(idx("pw_evals", i), d_pwe, n_pw * e);
+  }
+  /* the host-pointer form on the first case */
+  {
+    uint64_t *evals = read_bin(idx("evals", 0), n_evals * e), *pw = read_bin("pw", n_pw * rank * e);
+    uint64_t *chal = read_bin(idx("chal", 0), 5 * e), *ms = read_bin(idx("mask_sums", 0), 2 * e);
+    uint64_t verdict = ~UINT64_C(0), *sides = xmalloc(8 * e), *pwe = xmalloc(n_pw * e);
+    CK(rg_buckler_verify_checks(v, evals, pw, chal, ms, &verdict, sides, pwe));
+    write_bin("host_verdict", &verdict, 8);
+    write_bin("host_sides", sides, 8 * e);
+    write_bin("host_pw_evals", pwe, n_pw * e);
+    free(evals), free(pw), free(chal), free(ms), free(sides), free(pwe);
+  }
+
+  dfree_all();
+  rg_buckler_verifier_destroy(v);
+  rg_buckler_circuit_destroy(arith);
+  rg_buckler_circuit_destroy(sum);
+  rg_buckler_lincheck_destroy(lc);
+  for (int i = 0; i < N_CHK; i++) rg_buckler_checker_destroy(chk[i]);
+  rg_ntt_destroy(enc_plan);
+  rg_field_destroy(f);
+  free(q), free(rbase), free(xof), free(off64), free(pairs);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* mode = argc > 1 ? argv[1] : "";
   if (argc > 2) g_dir = argv[2];
@@ -634,6 +762,7 @@ int main(int argc, char** argv) {
   if (argc > 2 && strcmp(mode, "bigpoly") == 0) return mode_bigpoly();
   if (argc > 2 && strcmp(mode, "jindo") == 0) return mode_jindo();
   if (argc > 2 && strcmp(mode, "buckler") == 0) return mode_buckler();
-  fprintf(stderr, "usage: abi_replay layout|refuse [DIR] | bigpoly|jindo|buckler DIR\n");
+  if (argc > 2 && strcmp(mode, "bverify") == 0) return mode_bverify();
+  fprintf(stderr, "usage: abi_replay layout|refuse [DIR] | bigpoly|jindo|buckler|bverify DIR\n");
   return 3;
 }
