@@ -19,15 +19,10 @@
 #include "buckler_impl.hpp"
 #include "common.hpp"
 #include "field.hpp"
+#include "host_field.hpp"
 #include "ntt_plan.hpp"
 
 namespace rg {
-
-template <int L>
-__device__ __forceinline__ void cpy(uint64_t* d, const uint64_t* s) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = s[l];
-}
 
 // ---- Encoder ----------------------------------------------------------------------------------
 // element (b, i) of the [batch][emb][L] output: i < rank from src (the InvNTT output; src ==
@@ -41,15 +36,14 @@ __global__ __launch_bounds__(256) void embed_kernel(FieldParams<L> F, uint64_t* 
   uint64_t* o = out + gid * L;
   if (i < rank) {
     uint64_t x[L];
-    if (src) cpy<L>(x, src + (b * rank + i) * L);
-    else if (i == 0 && rnd) cpy<L>(x, o);
+    if (src) el_copy<L>(x, src + (b * rank + i) * L);
+    else if (i == 0 && rnd) el_copy<L>(x, o);
     if (i == 0 && rnd) f_sub<L>(x, x, rnd + b * L, F);  // Coeffs[0].Sub(Coeffs[0], Coeffs[rank])
-    if (src || (i == 0 && rnd)) cpy<L>(o, x);
+    if (src || (i == 0 && rnd)) el_copy<L>(o, x);
   } else if (i == rank && rnd) {
-    cpy<L>(o, rnd + b * L);  // Coeffs[rank].MustSetRandom()
+    el_copy<L>(o, rnd + b * L);  // Coeffs[rank].MustSetRandom()
   } else {
-#pragma unroll
-    for (int l = 0; l < L; ++l) o[l] = 0;  // Coeffs[i].SetUint64(0)
+    el_zero<L>(o);  // Coeffs[i].SetUint64(0)
   }
 }
 
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(256) void circuit_kernel(CircArgs<L> a) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= a.rank) return;
   uint64_t acc[L], bc[L];
-  cpy<L>(bc, a.bc);
+  el_copy<L>(bc, a.bc);
 #pragma unroll
   for (int l = 0; l < L; ++l) acc[l] = 0;  // pOut := NewPoly(true)
   uint32_t t = a.term_off[0];
@@ -86,14 +80,14 @@ __global__ __launch_bounds__(256) void circuit_kernel(CircArgs<L> a) {
     const uint32_t t1 = a.term_off[c + 1];
     for (; t < t1; ++t) {
       uint64_t term[L], x[L];
-      cpy<L>(term, a.coeffs + (size_t)t * L);  // term.Coeffs[j].Set(c.coeffs[i])
+      el_copy<L>(term, a.coeffs + (size_t)t * L);  // term.Coeffs[j].Set(c.coeffs[i])
       const int p = a.pw_idx[t];
       if (p >= 0) {  // MulTo(term, term, pwEcdNTT[...])
-        cpy<L>(x, a.pw + ((size_t)p * a.rank + j) * L);
+        el_copy<L>(x, a.pw + ((size_t)p * a.rank + j) * L);
         f_mul<L>(term, term, x, a.F);
       }
       for (uint32_t k = a.wit_off[t]; k < a.wit_off[t + 1]; ++k) {  // MulTo(term, term, wEcdNTT[...])
-        cpy<L>(x, a.w + ((size_t)a.wit[k] * a.rank + j) * L);
+        el_copy<L>(x, a.w + ((size_t)a.wit[k] * a.rank + j) * L);
         f_mul<L>(term, term, x, a.F);
       }
       f_add<L>(ev, ev, term, a.F);  // AddTo(eval, eval, term)
@@ -101,15 +95,13 @@ __global__ __launch_bounds__(256) void circuit_kernel(CircArgs<L> a) {
     f_mul<L>(ev, ev, bc, a.F);    // ScalarMulTo(eval, eval, batchConst)
     f_add<L>(acc, acc, ev, a.F);  // AddTo(pOut, pOut, eval)
   }
-  cpy<L>(a.out + j * L, acc);
+  el_copy<L>(a.out + j * L, acc);
 }
-
-static unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 
 template <int L>
 static rg_status embed_L(const rg_field* f, uint64_t* out, const uint64_t* src, long long rank, long long emb,
                          long long batch, const uint64_t* rnd, hipStream_t st) {
-  hipLaunchKernelGGL(embed_kernel<L>, dim3(blocks_of(batch * emb)), dim3(256), 0, st, field_params<L>(f), out, src,
+  hipLaunchKernelGGL(embed_kernel<L>, dim3(grid256(batch * emb)), dim3(256), 0, st, field_params<L>(f), out, src,
                      rank, emb, batch, rnd);
   return check_launch("buckler encode");
 }
@@ -119,26 +111,20 @@ static rg_status circuit_L(const rg_circuit* c, long long rank, const uint64_t* 
                            const uint64_t* pw, uint64_t* out, hipStream_t st) {
   CircArgs<L> a;
   a.F = field_params<L>(&c->f);
-  const char* base = c->prog.as<char>();
-  a.term_off = reinterpret_cast<const uint32_t*>(base);
-  a.pw_idx = reinterpret_cast<const int*>(base + c->off_pw);
-  a.wit_off = reinterpret_cast<const uint32_t*>(base + c->off_wo);
-  a.wit = reinterpret_cast<const uint32_t*>(base + c->off_wi);
-  a.coeffs = reinterpret_cast<const uint64_t*>(base + c->off_cf);
+  const CircProg p = circ_prog(c);
+  a.term_off = p.term_off;
+  a.pw_idx = p.pw_idx;
+  a.wit_off = p.wit_off;
+  a.wit = p.wit;
+  a.coeffs = p.coeffs;
   a.w = w;
   a.pw = pw;
   a.bc = bc;
   a.out = out;
   a.rank = rank;
-  a.nc = c->nc;
-  hipLaunchKernelGGL(circuit_kernel<L>, dim3(blocks_of(rank)), dim3(256), 0, st, a);
+  a.nc = p.nc;
+  hipLaunchKernelGGL(circuit_kernel<L>, dim3(grid256(rank)), dim3(256), 0, st, a);
   return check_launch("buckler evalCircuit");
-}
-
-static bool lt_q(const uint64_t* x, const rg_field* f) {
-  for (int i = f->L - 1; i >= 0; --i)
-    if (x[i] != f->q[i]) return x[i] < f->q[i];
-  return false;
 }
 
 }  // namespace rg
@@ -182,8 +168,7 @@ rg_status rg_buckler_encode(const rg_ntt* t, size_t embed_rank, uint64_t* out, c
   if (rand) RG_TRY(dr.upload(rand, L * 8));
   RG_TRY(rg_buckler_encode_dev(t, embed_rank, dout.as<uint64_t>(), dv.as<uint64_t>(), 1,
                                rand ? dr.as<uint64_t>() : nullptr, nullptr, nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, embed_rank * L * 8, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, embed_rank * L * 8);
 }
 
 rg_status rg_buckler_circuit_create(const rg_field* f, size_t n_constraints, const size_t* term_off,
@@ -209,8 +194,8 @@ rg_status rg_buckler_circuit_create(const rg_field* f, size_t n_constraints, con
     return RG_ERR_INVALID;
   }
   for (size_t t = 0; t < nt; ++t) {
-    if (!lt_q(coeffs + t * f->L, f) || pw_idx[t] >= (1LL << 31) || wit_off[t + 1] < wit_off[t] ||
-        wit_off[t + 1] >= (1u << 31)) {
+    if (HostField::geq(coeffs + t * f->L, f->q, f->L) || pw_idx[t] >= (1LL << 31) ||
+        wit_off[t + 1] < wit_off[t] || wit_off[t + 1] >= (1u << 31)) {
       delete c;
       return RG_ERR_INVALID;
     }
@@ -276,8 +261,7 @@ rg_status rg_buckler_eval_circuit(const rg_circuit* c, size_t rank, const uint64
   RG_TRY(dout.alloc(poly + 8));
   RG_TRY(rg_buckler_eval_circuit_dev(c, rank, dbc.as<uint64_t>(), n_w ? dw.as<uint64_t>() : nullptr, n_w,
                                      n_pw ? dpw.as<uint64_t>() : nullptr, n_pw, dout.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, poly, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, poly);
 }
 
 }  // extern "C"

@@ -43,12 +43,6 @@ struct DcmpConst {
   uint64_t one[L], neg_one[L];
 };
 
-template <int L>
-__device__ __forceinline__ void load_el(uint64_t* d, const uint64_t* s) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = s[l];
-}
-
 // ---- prover.go:77-86: a lane per coefficient, grid (rank blocks, batch) ---------------------
 // The base index j is uniform, so base[j] comes through scalar loads.  For fixed j consecutive
 // lanes store consecutive elements of digit witness j; the L words of an element leave as 16-byte
@@ -62,14 +56,14 @@ __global__ __launch_bounds__(256) void dcmp_inf_kernel(DcmpConst<L> K, uint64_t*
   if (i >= rank) return;
   const long long k = blockIdx.y;
   uint64_t x[L], c[L];
-  load_el<L>(x, w + (k * rank + i) * L);
+  el_copy<L>(x, w + (k * rank + i) * L);
   Dcmp<L> d;
   dcmp_init<L>(d, x, K.F);
   dcmp_unit<L>(c, d, K.one, K.neg_one);
   uint64_t* o = out + (k * nb * rank + i) * L;
   for (long long j = 0; j < nb; ++j) {
     uint64_t b[L], v[L];
-    load_el<L>(b, base + j * L);
+    el_copy<L>(b, base + j * L);
     const uint64_t mask = 0 - (uint64_t)dcmp_step<L>(d, b);
 #pragma unroll
     for (int l = 0; l < L; ++l) v[l] = c[l] & mask;
@@ -88,20 +82,17 @@ __global__ __launch_bounds__(256) void dcmp_proj_kernel(DcmpConst<L> K, uint64_t
                                                         long long rank) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= rank) return;
-  if (t >= kDcmpProjRows * nb) {
-#pragma unroll
-    for (int l = 0; l < L; ++l) out[t * L + l] = 0;
-  }
+  if (t >= kDcmpProjRows * nb) el_zero<L>(out + t * L);
   if (t >= kDcmpProjRows) return;
   uint64_t x[L], c[L];
-  load_el<L>(x, w + t * L);
+  el_copy<L>(x, w + t * L);
   Dcmp<L> d;
   dcmp_init<L>(d, x, K.F);
   dcmp_unit<L>(c, d, K.one, K.neg_one);
   uint64_t* o = out + t * nb * L;
   for (long long j = 0; j < nb; ++j) {
     uint64_t b[L];
-    load_el<L>(b, base + j * L);
+    el_copy<L>(b, base + j * L);
     const uint64_t mask = 0 - (uint64_t)dcmp_step<L>(d, b);
 #pragma unroll
     for (int l = 0; l < L; ++l) o[j * L + l] = c[l] & mask;
@@ -126,7 +117,7 @@ __global__ __launch_bounds__(kTwoBlock) void dcmp_two_partial_kernel(FieldParams
     const long long i = i0 + r * kTwoBlock + tid;
     if (i < rank) {
       uint64_t x[L];
-      load_el<L>(x, w + (k * rank + i) * L);
+      el_copy<L>(x, w + (k * rank + i) * L);
       f_mul<L>(x, x, x, F);
       f_add<L>(acc, acc, x, F);
     }
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(kTwoBlock) void dcmp_two_partial_kernel(FieldParams
   for (int h = kTwoBlock / 2; h > 0; h >>= 1) {
     if (tid < h) {
       uint64_t y[L];
-      load_el<L>(y, red + (tid + h) * L);
+      el_copy<L>(y, red + (tid + h) * L);
       f_add<L>(acc, acc, y, F);
 #pragma unroll
       for (int l = 0; l < L; ++l) red[tid * L + l] = acc[l];
@@ -171,7 +162,7 @@ __global__ __launch_bounds__(256) void dcmp_two_final_kernel(DcmpConst<L> K, uin
     for (int l = 0; l < L; ++l) acc[l] = 0;
     for (long long ch = 0; ch < chunks; ++ch) {
       uint64_t y[L];
-      load_el<L>(y, partial + (k * chunks + ch) * L);
+      el_copy<L>(y, partial + (k * chunks + ch) * L);
       f_add<L>(acc, acc, y, K.F);
     }
     if (sq && i == 0) {
@@ -184,7 +175,7 @@ __global__ __launch_bounds__(256) void dcmp_two_final_kernel(DcmpConst<L> K, uin
     const long long j1 = min(nb, i0 + (long long)blockDim.x);
     for (long long j = 0; j < j1; ++j) {
       uint64_t b[L];
-      load_el<L>(b, base + j * L);
+      el_copy<L>(b, base + j * L);
       const uint64_t mask = 0 - (uint64_t)(dcmp_step<L>(d, b) && j == i);
 #pragma unroll
       for (int l = 0; l < L; ++l) v[l] |= c[l] & mask;
@@ -205,8 +196,6 @@ static DcmpConst<L> consts(const rg_dcmp* h) {
   return K;
 }
 
-static unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
-static bool dcmp_supported_L(int L) { return L == 1 || L == 2 || L == 4 || L == 7 || L == 14; }
 static long long two_chunks(long long rank) { return (rank + kTwoChunk - 1) / kTwoChunk; }
 
 constexpr size_t kMaxRank = (size_t)1 << 30;
@@ -224,14 +213,14 @@ static rg_status ensure_base(const rg_dcmp* h) {
 template <int L>
 static rg_status inf_L(const rg_dcmp* h, const uint64_t* w, long long batch, long long rank, uint64_t* out,
                        hipStream_t st) {
-  hipLaunchKernelGGL(dcmp_inf_kernel<L>, dim3(blocks256(rank), (unsigned)batch), dim3(256), 0, st, consts<L>(h), out, w,
+  hipLaunchKernelGGL(dcmp_inf_kernel<L>, dim3(grid256(rank), (unsigned)batch), dim3(256), 0, st, consts<L>(h), out, w,
                      h->base.as<uint64_t>(), h->nb, rank);
   return check_launch("dcmp inf");
 }
 
 template <int L>
 static rg_status proj_L(const rg_dcmp* h, const uint64_t* w, long long rank, uint64_t* out, hipStream_t st) {
-  hipLaunchKernelGGL(dcmp_proj_kernel<L>, dim3(blocks256(rank)), dim3(256), 0, st, consts<L>(h), out, w,
+  hipLaunchKernelGGL(dcmp_proj_kernel<L>, dim3(grid256(rank)), dim3(256), 0, st, consts<L>(h), out, w,
                      h->base.as<uint64_t>(), h->nb, rank);
   return check_launch("dcmp proj");
 }
@@ -244,7 +233,7 @@ static rg_status two_L(const rg_dcmp* h, const uint64_t* w, long long batch, lon
   hipLaunchKernelGGL(dcmp_two_partial_kernel<L>, dim3((unsigned)chunks, (unsigned)batch), dim3(kTwoBlock), 0, st, K.F,
                      scratch, w, rank);
   RG_TRY(check_launch("dcmp two-norm squares"));
-  hipLaunchKernelGGL(dcmp_two_final_kernel<L>, dim3(blocks256(rank), (unsigned)batch), dim3(256), 0, st, K, out, sq,
+  hipLaunchKernelGGL(dcmp_two_final_kernel<L>, dim3(grid256(rank), (unsigned)batch), dim3(256), 0, st, K, out, sq,
                      scratch, h->base.as<uint64_t>(), h->nb, rank, chunks);
   return check_launch("dcmp two-norm digits");
 }
@@ -282,7 +271,7 @@ rg_status rg_buckler_dcmp_create(const rg_field* f, const uint64_t* base, size_t
   if (!f || !out) return RG_ERR_INVALID;
   *out = nullptr;
   if (!base || nb == 0 || nb > kMaxRank) return RG_ERR_INVALID;
-  if (!dcmp_supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  if (!limbs_supported(f->L)) return RG_ERR_UNSUPPORTED;
   const int L = f->L;
   for (size_t j = 0; j < nb; ++j) {  // b_j >= 1 (dcmp.hpp)
     uint64_t orv = 0;
@@ -340,8 +329,7 @@ rg_status rg_buckler_dcmp_inf(const rg_dcmp* h, const uint64_t* w, size_t batch,
   RG_TRY(dw.upload(w, in_bytes));
   RG_TRY(dout.alloc(out_bytes));
   RG_TRY(rg_buckler_dcmp_inf_dev(h, dw.as<uint64_t>(), batch, rank, dout.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, out_bytes);
 }
 
 rg_status rg_buckler_dcmp_proj(const rg_dcmp* h, const uint64_t* w, size_t rank, uint64_t* out) {
@@ -351,8 +339,7 @@ rg_status rg_buckler_dcmp_proj(const rg_dcmp* h, const uint64_t* w, size_t rank,
   RG_TRY(dw.upload(w, kDcmpProjRows * e));  // only w[0..127] is read
   RG_TRY(dout.alloc(rank * e));
   RG_TRY(rg_buckler_dcmp_proj_dev(h, dw.as<uint64_t>(), rank, dout.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, rank * e, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, rank * e);
 }
 
 rg_status rg_buckler_dcmp_two(const rg_dcmp* h, const uint64_t* w, size_t batch, size_t rank, uint64_t* out,
@@ -367,8 +354,8 @@ rg_status rg_buckler_dcmp_two(const rg_dcmp* h, const uint64_t* w, size_t batch,
   RG_TRY(dscr.alloc(rg_buckler_dcmp_two_scratch_bytes(h, batch, rank)));
   RG_TRY(rg_buckler_dcmp_two_dev(h, dw.as<uint64_t>(), batch, rank, dout.as<uint64_t>(), dsq.as<uint64_t>(),
                                  dscr.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, batch * rank * e, hipMemcpyDeviceToHost));
-  if (sq) RG_HIP(hipMemcpy(sq, dsq.p, batch * e, hipMemcpyDeviceToHost));
+  RG_TRY(dout.download(out, batch * rank * e));
+  if (sq) RG_TRY(dsq.download(sq, batch * e));
   return RG_OK;
 }
 

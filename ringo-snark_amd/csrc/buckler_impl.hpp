@@ -1,8 +1,11 @@
-// buckler_impl.hpp -- the handle definitions the Buckler units share: the constraint program
-// (buckler.hip), the checkers and the linear check (buckler_lin.hip), read by the verifier's checks
-// (buckler_verify.hip).  Declarations only: every kernel and launcher stays in its unit, and the
-// verifier reaches them through the `_dev` entries of include/ringo.h.
+// buckler_impl.hpp -- what the Buckler units share: the handle definitions of the constraint
+// program (buckler.hip), the checkers and the linear check (buckler_lin.hip), and the one decode of
+// each handle's device program into pointers (circ_prog, lin_prog), read by the prover's passes and
+// by the verifier's checks (buckler_verify.hip).  Every kernel and launcher stays in its unit, and
+// the verifier reaches them through the `_dev` entries of include/ringo.h.
 #pragma once
+#include <string.h>
+
 #include <vector>
 
 #include "common.hpp"
@@ -43,3 +46,47 @@ struct rg_lincheck {
   long long max_w = -1;
   rg::DevBuf prog;  // pair_off [n_chk+1] u32 | pairs [n_pairs][2] u32 (wOut, wIn)
 };
+
+namespace rg {
+
+struct CircProg {  // rg_circuit::prog as device pointers; nc < 0: no circuit (c == nullptr)
+  const uint32_t* term_off;
+  const int* pw_idx;
+  const uint32_t* wit_off;
+  const uint32_t* wit;
+  const uint64_t* coeffs;
+  int nc;
+};
+
+inline CircProg circ_prog(const rg_circuit* c) {
+  CircProg p;
+  memset(&p, 0, sizeof p);
+  p.nc = -1;
+  if (!c) return p;
+  const char* base = c->prog.as<char>();
+  p.term_off = reinterpret_cast<const uint32_t*>(base);
+  p.pw_idx = reinterpret_cast<const int*>(base + c->off_pw);
+  p.wit_off = reinterpret_cast<const uint32_t*>(base + c->off_wo);
+  p.wit = reinterpret_cast<const uint32_t*>(base + c->off_wi);
+  p.coeffs = reinterpret_cast<const uint64_t*>(base + c->off_cf);
+  p.nc = c->nc;
+  return p;
+}
+
+struct LinProg {  // rg_lincheck::prog as device pointers; all zero: no linear check (lc == nullptr)
+  const uint32_t* pair_off;
+  const uint32_t* pairs;
+  int n_chk, n_pairs;
+};
+
+inline LinProg lin_prog(const rg_lincheck* lc) {
+  LinProg p = {nullptr, nullptr, 0, 0};
+  if (!lc) return p;
+  p.n_chk = (int)lc->chk.size();
+  p.pair_off = lc->prog.as<uint32_t>();
+  p.pairs = p.pair_off + p.n_chk + 1;
+  p.n_pairs = lc->n_pairs;
+  return p;
+}
+
+}  // namespace rg

@@ -16,7 +16,6 @@
 // Every sum and product is the canonical Montgomery arithmetic of field.hpp, so every output limb
 // equals the reference's.  All randomness and all challenges are injected.
 #include <algorithm>
-#include <cstring>
 #include <vector>
 
 #include "buckler_impl.hpp"
@@ -31,33 +30,17 @@ constexpr int kProjRows = 128;   // linear.go:99
 constexpr int kProjChunk = 128;  // columns per workgroup of the projection transform
 constexpr int kPowBlock = 16;    // exponents per lane of the power vector
 
-template <int L>
-struct El {
-  uint64_t v[L];
-};
-
-template <int L>
-__device__ __forceinline__ void cpl(uint64_t* d, const uint64_t* s) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = s[l];
-}
-template <int L>
-__device__ __forceinline__ void zero(uint64_t* d) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = 0;
-}
-
 // ---- NTT checker: vOut[i] = v[rank-1-i] * scale (linear.go:39-41) ------------------------------
 template <int L>
-__global__ __launch_bounds__(256) void revscale_kernel(FieldParams<L> F, El<L> scale, uint64_t* out, const uint64_t* v,
-                                                       long long rank, long long batch) {
+__global__ __launch_bounds__(256) void revscale_kernel(FieldParams<L> F, Elem<L> scale, uint64_t* out,
+                                                       const uint64_t* v, long long rank, long long batch) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= batch * rank) return;
   const long long b = gid / rank, i = gid % rank;
   uint64_t x[L];
-  cpl<L>(x, v + (b * rank + (rank - 1 - i)) * L);
+  el_copy<L>(x, v + (b * rank + (rank - 1 - i)) * L);
   f_mul<L>(x, x, scale.v, F);
-  cpl<L>(out + gid * L, x);
+  el_copy<L>(out + gid * L, x);
 }
 
 // ---- projection checker ---------------------------------------------------------------------
@@ -85,7 +68,7 @@ __global__ __launch_bounds__(kProjRows) void proj_fwd_kernel(FieldParams<L> F, u
   const long long chunks = gridDim.x, b = blockIdx.y, j0 = (long long)blockIdx.x * kProjChunk;
   const long long j = j0 + tid;
   if (j < rank) {
-    cpl<L>(sv + tid * L, v + (b * rank + j) * L);
+    el_copy<L>(sv + tid * L, v + (b * rank + j) * L);
 #pragma unroll
     for (int w = 0; w < 4; ++w) sm[tid * 4 + w] = bits[j * 4 + w];
   }
@@ -93,7 +76,7 @@ __global__ __launch_bounds__(kProjRows) void proj_fwd_kernel(FieldParams<L> F, u
   const int cnt = (int)min((long long)kProjChunk, rank - j0);
   const int word = tid >> 5, bit = tid & 31;
   uint64_t acc[L];
-  zero<L>(acc);
+  el_zero<L>(acc);
 #pragma unroll 1
   for (int jj = 0; jj < cnt; ++jj) {
     const uint64_t m = 0 - (uint64_t)((sm[jj * 4 + word] >> bit) & 1u);
@@ -102,7 +85,7 @@ __global__ __launch_bounds__(kProjRows) void proj_fwd_kernel(FieldParams<L> F, u
     for (int l = 0; l < L; ++l) x[l] = sv[jj * L + l] & m;
     f_add<L>(acc, acc, x, F);
   }
-  cpl<L>(partial + ((b * chunks + blockIdx.x) * kProjRows + tid) * L, acc);
+  el_copy<L>(partial + ((b * chunks + blockIdx.x) * kProjRows + tid) * L, acc);
 }
 
 // stage 2: the chunk partials summed in chunk order; rows 128 .. rank-1 are zero (linear.go:120-122)
@@ -113,15 +96,15 @@ __global__ __launch_bounds__(256) void proj_sum_kernel(FieldParams<L> F, uint64_
   if (gid >= batch * rank) return;
   const long long b = gid / rank, i = gid % rank;
   uint64_t acc[L];
-  zero<L>(acc);
+  el_zero<L>(acc);
   if (i < kProjRows) {
     for (long long c = 0; c < chunks; ++c) {
       uint64_t x[L];
-      cpl<L>(x, partial + ((b * chunks + c) * kProjRows + i) * L);
+      el_copy<L>(x, partial + ((b * chunks + c) * kProjRows + i) * L);
       f_add<L>(acc, acc, x, F);
     }
   }
-  cpl<L>(out + gid * L, acc);
+  el_copy<L>(out + gid * L, acc);
 }
 
 // TransposeTo (linear.go:125-137): a lane per column, v[0..127] in LDS
@@ -131,11 +114,11 @@ __global__ __launch_bounds__(kProjRows) void proj_tr_kernel(FieldParams<L> F, ui
   __shared__ uint64_t sv[kProjRows * L];
   const int tid = threadIdx.x;
   const long long b = blockIdx.y, j = (long long)blockIdx.x * kProjRows + tid;
-  cpl<L>(sv + tid * L, v + (b * rank + tid) * L);  // rank >= 128
+  el_copy<L>(sv + tid * L, v + (b * rank + tid) * L);  // rank >= 128
   __syncthreads();
   if (j >= rank) return;
   uint64_t acc[L];
-  zero<L>(acc);
+  el_zero<L>(acc);
 #pragma unroll 1
   for (int w = 0; w < 4; ++w) {
     const uint32_t mw = bits[j * 4 + w];
@@ -148,7 +131,7 @@ __global__ __launch_bounds__(kProjRows) void proj_tr_kernel(FieldParams<L> F, ui
       f_add<L>(acc, acc, x, F);
     }
   }
-  cpl<L>(out + (b * rank + j) * L, acc);
+  el_copy<L>(out + (b * rank + j) * L, acc);
 }
 
 // ---- recompose checker (linear.go:155-180) ----------------------------------------------------
@@ -160,17 +143,17 @@ __global__ __launch_bounds__(256) void recompose_fwd_kernel(FieldParams<L> F, ui
   if (gid >= batch * rank) return;
   const long long b = gid / rank, i = gid % rank;
   uint64_t acc[L];
-  zero<L>(acc);
+  el_zero<L>(acc);
   if (i < rank / nb) {
     for (long long j = 0; j < nb; ++j) {
       uint64_t x[L], y[L];
-      cpl<L>(x, base + j * L);
-      cpl<L>(y, v + (b * rank + i * nb + j) * L);
+      el_copy<L>(x, base + j * L);
+      el_copy<L>(y, v + (b * rank + i * nb + j) * L);
       f_mul<L>(x, x, y, F);
       f_add<L>(acc, acc, x, F);
     }
   }
-  cpl<L>(out + gid * L, acc);
+  el_copy<L>(out + gid * L, acc);
 }
 
 template <int L>
@@ -181,34 +164,34 @@ __global__ __launch_bounds__(256) void recompose_tr_kernel(FieldParams<L> F, uin
   if (gid >= batch * rank) return;
   const long long b = gid / rank, k = gid % rank;
   uint64_t x[L];
-  zero<L>(x);
+  el_zero<L>(x);
   if (k < (rank / nb) * nb) {
     uint64_t y[L];
-    cpl<L>(x, base + (k % nb) * L);
-    cpl<L>(y, v + (b * rank + k / nb) * L);
+    el_copy<L>(x, base + (k % nb) * L);
+    el_copy<L>(y, v + (b * rank + k / nb) * L);
     f_mul<L>(x, x, y, F);
   }
-  cpl<L>(out + gid * L, x);
+  el_copy<L>(out + gid * L, x);
 }
 
 // ---- power vector (prover.go:409-413) ---------------------------------------------------------
 template <int L>
-__global__ __launch_bounds__(256) void powers_kernel(FieldParams<L> F, El<L> one, const uint64_t* c, uint64_t* out,
-                                                     long long n) {
+__global__ __launch_bounds__(256) void powers_kernel(FieldParams<L> F, Elem<L> one, const uint64_t* c,
+                                                     uint64_t* out, long long n) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long e0 = t * kPowBlock;
   if (e0 >= n) return;
   uint64_t cv[L], p[L], sq[L];
-  cpl<L>(cv, c);
-  cpl<L>(p, one.v);
-  cpl<L>(sq, cv);
+  el_copy<L>(cv, c);
+  el_copy<L>(p, one.v);
+  el_copy<L>(sq, cv);
   for (unsigned long long e = (unsigned long long)e0; e; e >>= 1) {  // p = c^e0
     if (e & 1) f_mul<L>(p, p, sq, F);
     f_mul<L>(sq, sq, sq, F);
   }
   const long long e1 = min(n, e0 + kPowBlock);
   for (long long e = e0; e < e1; ++e) {
-    cpl<L>(out + e * L, p);
+    el_copy<L>(out + e * L, p);
     f_mul<L>(p, p, cv, F);
   }
 }
@@ -222,17 +205,17 @@ __global__ __launch_bounds__(256) void mask_kernel(FieldParams<L> F, uint64_t* m
   const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= emb) return;
   uint64_t x[L];
-  zero<L>(x);
+  el_zero<L>(x);
   if (k < mask_rank) {
-    cpl<L>(x, r + k * L);
-    if (k == 0) cpl<L>(mask_sum, x);  // maskSum := mask.Coeffs[0] before the loop
+    el_copy<L>(x, r + k * L);
+    if (k == 0) el_copy<L>(mask_sum, x);  // maskSum := mask.Coeffs[0] before the loop
     if (k + rank < mask_rank) {
       uint64_t y[L];
-      cpl<L>(y, r + (k + rank) * L);
+      el_copy<L>(y, r + (k + rank) * L);
       f_sub<L>(x, x, y, F);
     }
   }
-  cpl<L>(mask + k * L, x);
+  el_copy<L>(mask + k * L, x);
 }
 
 // ---- check tail: quo = quoPoly[:n_quo], remLo[i] = rem[i+1], remHi = zeros | remLo ---------
@@ -241,15 +224,15 @@ __global__ __launch_bounds__(256) void tail_kernel(uint64_t* quo, uint64_t* rem_
                                                    const uint64_t* quo_poly, const uint64_t* rem, long long n_quo,
                                                    long long rank, long long jindo_rank) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_quo) cpl<L>(quo + i * L, quo_poly + i * L);
+  if (i < n_quo) el_copy<L>(quo + i * L, quo_poly + i * L);
   if (!rem_lo) return;
-  if (i < rank - 1) cpl<L>(rem_lo + i * L, rem + (i + 1) * L);
+  if (i < rank - 1) el_copy<L>(rem_lo + i * L, rem + (i + 1) * L);
   if (i < jindo_rank) {
     const long long z = jindo_rank - (rank - 1);
     uint64_t x[L];
-    zero<L>(x);
-    if (i >= z) cpl<L>(x, rem + (i - z + 1) * L);
-    cpl<L>(rem_hi + i * L, x);
+    el_zero<L>(x);
+    if (i >= z) el_copy<L>(x, rem + (i - z + 1) * L);
+    el_copy<L>(rem_hi + i * L, x);
   }
 }
 
@@ -273,48 +256,34 @@ __global__ __launch_bounds__(256) void lin_kernel(LinArgs<L> a) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= a.emb) return;
   uint64_t ev[L], bc[L], e0[L];
-  zero<L>(ev);  // eval := NewPoly(true)
-  cpl<L>(bc, a.bc);
-  cpl<L>(e0, a.ecd + j * L);
+  el_zero<L>(ev);  // eval := NewPoly(true)
+  el_copy<L>(bc, a.bc);
+  el_copy<L>(e0, a.ecd + j * L);
   uint32_t k = a.pair_off[0];
   for (int c = 0; c < a.n_chk; ++c) {
     const uint32_t k1 = a.pair_off[c + 1];
     if (k == k1) continue;
     uint64_t tr[L];
-    cpl<L>(tr, a.ecd + ((size_t)(1 + c) * a.emb + j) * L);
+    el_copy<L>(tr, a.ecd + ((size_t)(1 + c) * a.emb + j) * L);
     for (; k < k1; ++k) {
       uint64_t term[L], x[L];
-      cpl<L>(x, a.w + ((size_t)a.pairs[2 * k + 1] * a.emb + j) * L);
+      el_copy<L>(x, a.w + ((size_t)a.pairs[2 * k + 1] * a.emb + j) * L);
       f_mul<L>(term, tr, x, a.F);  // MulTo(term, linCheckEcdTr, wIn)
-      cpl<L>(x, a.w + ((size_t)a.pairs[2 * k] * a.emb + j) * L);
+      el_copy<L>(x, a.w + ((size_t)a.pairs[2 * k] * a.emb + j) * L);
       f_mul<L>(x, e0, x, a.F);
       f_sub<L>(term, term, x, a.F);  // MulSubTo(term, linCheckEcd, wOut)
       f_mul<L>(ev, ev, bc, a.F);     // ScalarMulTo(eval, eval, batchConst)
       f_add<L>(ev, ev, term, a.F);   // AddTo(eval, eval, term)
     }
   }
-  cpl<L>(a.out + j * L, ev);
+  el_copy<L>(a.out + j * L, ev);
 }
 
 // ---- host side ----------------------------------------------------------------------------------
 template <int L>
-static El<L> el(const uint64_t* x) {
-  El<L> e;
-  memcpy(e.v, x, 8 * L);
-  return e;
-}
-
-static unsigned grid256(long long n) { return (unsigned)((n + 255) / 256); }
-static bool is_pow2(long long n) { return n > 0 && !(n & (n - 1)); }
-static bool supported_L(int L) { return L == 1 || L == 2 || L == 4 || L == 7 || L == 14; }
-static bool same_field(const rg_field* a, const rg_field* b) {
-  return a->L == b->L && memcmp(a->q, b->q, 8 * a->L) == 0;
-}
-
-template <int L>
 static rg_status revscale_L(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
   hipLaunchKernelGGL(revscale_kernel<L>, dim3(grid256(batch * c->rank)), dim3(256), 0, st, field_params<L>(&c->f),
-                     el<L>(c->scale), out, v, c->rank, batch);
+                     elem<L>(c->scale), out, v, c->rank, batch);
   return check_launch("ntt checker transpose");
 }
 
@@ -354,7 +323,7 @@ static rg_status recompose_L(const rg_linchecker* c, bool tr, uint64_t* out, con
 template <int L>
 static rg_status powers_L(const rg_field* f, const uint64_t* c, long long n, uint64_t* out, hipStream_t st) {
   const long long lanes = (n + kPowBlock - 1) / kPowBlock;
-  hipLaunchKernelGGL(powers_kernel<L>, dim3(grid256(lanes)), dim3(256), 0, st, field_params<L>(f), el<L>(f->one), c,
+  hipLaunchKernelGGL(powers_kernel<L>, dim3(grid256(lanes)), dim3(256), 0, st, field_params<L>(f), elem<L>(f->one), c,
                      out, n);
   return check_launch("powers");
 }
@@ -383,14 +352,15 @@ static rg_status lin_L(const rg_lincheck* lc, const uint64_t* ecd, const uint64_
                        long long emb, hipStream_t st) {
   LinArgs<L> a;
   a.F = field_params<L>(ntt_field(lc->emb));
-  a.pair_off = lc->prog.as<uint32_t>();
-  a.pairs = a.pair_off + lc->chk.size() + 1;
+  const LinProg p = lin_prog(lc);
+  a.pair_off = p.pair_off;
+  a.pairs = p.pairs;
   a.ecd = ecd;
   a.w = w;
   a.bc = bc;
   a.out = out;
   a.emb = emb;
-  a.n_chk = (int)lc->chk.size();
+  a.n_chk = p.n_chk;
   hipLaunchKernelGGL(lin_kernel<L>, dim3(grid256(emb)), dim3(256), 0, st, a);
   return check_launch("linCheck");
 }
@@ -459,8 +429,7 @@ static rg_status checker_host(const rg_linchecker* c, bool tr, uint64_t* out, co
   RG_TRY(dout.alloc(bytes));
   RG_TRY(dscr.alloc(rg_buckler_checker_scratch_bytes(c, 1)));
   RG_TRY(checker_apply(c, tr, dout.as<uint64_t>(), dv.as<uint64_t>(), 1, dscr.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, bytes);
 }
 
 static rg_linchecker* new_checker(int kind, const rg_field* f, size_t rank) {
@@ -500,7 +469,7 @@ rg_status rg_buckler_checker_create_aut(const rg_field* f, size_t rank, long lon
   if (!f || !out) return RG_ERR_INVALID;
   *out = nullptr;
   if (!rank_ok(rank) || !is_pow2((long long)rank) || (idx & 1) == 0) return RG_ERR_INVALID;
-  if (!supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  if (!limbs_supported(f->L)) return RG_ERR_UNSUPPORTED;
   auto c = new_checker(RG_CHK_AUT, f, rank);
   const long long n2 = 2 * (long long)rank;
   c->idx = ((idx % n2) + n2) % n2;
@@ -514,7 +483,7 @@ rg_status rg_buckler_checker_create_proj(const rg_field* f, size_t rank, rg_linc
   if (!f || !out) return RG_ERR_INVALID;
   *out = nullptr;
   if (!rank_ok(rank) || rank < (size_t)kProjRows) return RG_ERR_INVALID;  // vOut holds the 128 rows
-  if (!supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  if (!limbs_supported(f->L)) return RG_ERR_UNSUPPORTED;
   *out = new_checker(RG_CHK_PROJ, f, rank);
   return RG_OK;
 }
@@ -524,7 +493,7 @@ rg_status rg_buckler_checker_create_recompose(const rg_field* f, size_t rank, co
   if (!f || !out) return RG_ERR_INVALID;
   *out = nullptr;
   if (!rank_ok(rank) || nb == 0 || nb > ((size_t)1 << 30) || !base) return RG_ERR_INVALID;
-  if (!supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  if (!limbs_supported(f->L)) return RG_ERR_UNSUPPORTED;
   for (size_t j = 0; j < nb; ++j)
     if (HostField::geq(base + j * f->L, f->q, f->L)) return RG_ERR_INVALID;
   auto c = new_checker(RG_CHK_RECOMPOSE, f, rank);
@@ -597,8 +566,7 @@ rg_status rg_buckler_powers(const rg_field* f, const uint64_t* c, size_t n, uint
   RG_TRY(dc.upload(c, f->L * 8));
   RG_TRY(dout.alloc(n * f->L * 8));
   RG_TRY(rg_buckler_powers_dev(f, dc.as<uint64_t>(), n, dout.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, n * f->L * 8, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, n * f->L * 8);
 }
 
 // ---- sumCheckMask -----------------------------------------------------------------------------
@@ -624,9 +592,8 @@ rg_status rg_buckler_sumcheck_mask(const rg_field* f, size_t rank, size_t mask_r
   RG_TRY(ds.alloc(e));
   RG_TRY(rg_buckler_sumcheck_mask_dev(f, rank, mask_rank, emb_rank, dr.as<uint64_t>(), dm.as<uint64_t>(),
                                       ds.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(mask, dm.p, emb_rank * e, hipMemcpyDeviceToHost));
-  RG_HIP(hipMemcpy(mask_sum, ds.p, e, hipMemcpyDeviceToHost));
-  return RG_OK;
+  RG_TRY(dm.download(mask, emb_rank * e));
+  return ds.download(mask_sum, e);
 }
 
 // ---- check tail ---------------------------------------------------------------------------------
@@ -680,10 +647,10 @@ rg_status rg_buckler_check_finish(const rg_ntt* emb_plan, size_t rank, const uin
                                      mask ? dmk.as<uint64_t>() : nullptr, n_quo, jindo_rank, dq.as<uint64_t>(),
                                      rem_lo ? dlo.as<uint64_t>() : nullptr, rem_lo ? dhi.as<uint64_t>() : nullptr,
                                      dscr.as<uint64_t>(), nullptr));
-  if (n_quo) RG_HIP(hipMemcpy(quo, dq.p, n_quo * e, hipMemcpyDeviceToHost));
+  if (n_quo) RG_TRY(dq.download(quo, n_quo * e));
   if (rem_lo) {
-    if (rank > 1) RG_HIP(hipMemcpy(rem_lo, dlo.p, (rank - 1) * e, hipMemcpyDeviceToHost));
-    if (jindo_rank) RG_HIP(hipMemcpy(rem_hi, dhi.p, jindo_rank * e, hipMemcpyDeviceToHost));
+    if (rank > 1) RG_TRY(dlo.download(rem_lo, (rank - 1) * e));
+    if (jindo_rank) RG_TRY(dhi.download(rem_hi, jindo_rank * e));
   }
   return RG_OK;
 }
@@ -792,9 +759,9 @@ rg_status rg_buckler_lin_check(const rg_lincheck* lc, const uint64_t* batch_cons
   RG_TRY(rg_buckler_lin_check_dev(lc, dbc.as<uint64_t>(), dlc.as<uint64_t>(), dmk.as<uint64_t>(),
                                   n_w ? dw.as<uint64_t>() : nullptr, n_w, jindo_rank, dq.as<uint64_t>(),
                                   dlo.as<uint64_t>(), dhi.as<uint64_t>(), dscr.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(quo, dq.p, rank * e, hipMemcpyDeviceToHost));
-  if (rank > 1) RG_HIP(hipMemcpy(rem_lo, dlo.p, (rank - 1) * e, hipMemcpyDeviceToHost));
-  if (jindo_rank) RG_HIP(hipMemcpy(rem_hi, dhi.p, jindo_rank * e, hipMemcpyDeviceToHost));
+  RG_TRY(dq.download(quo, rank * e));
+  if (rank > 1) RG_TRY(dlo.download(rem_lo, (rank - 1) * e));
+  if (jindo_rank) RG_TRY(dhi.download(rem_hi, jindo_rank * e));
   return RG_OK;
 }
 

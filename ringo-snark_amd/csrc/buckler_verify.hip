@@ -15,7 +15,6 @@
 //   sum_c (bc * ev_c)                    = bc * sum_c ev_c                 (evalCircuit, one bc for all c)
 //   Horner  e = e bc + t_k, k < n; e bc + m = sum_k t_k bc^(n-k) + m         (linCheck's chain)
 //   (bc * S) * bc                        = S * bc^2                         (sumCheck's second scale)
-#include <cstring>
 #include <string>
 
 #include "buckler_impl.hpp"
@@ -41,24 +40,10 @@ constexpr int kDecideLanes = 256;
 enum { S_VANISH = 0, S_SHIFT, S_BC2, S_CIRC0, S_CIRC1, S_LIN, S_P0, S_COUNT = S_P0 + 9 };
 
 template <int L>
-struct VEl {
-  uint64_t v[L];
-};
-
-struct CircProg {  // the rg_circuit program (buckler.hip); nc < 0: the check is absent
-  const uint32_t* term_off;
-  const int* pw_idx;
-  const uint32_t* wit_off;
-  const uint32_t* wit;
-  const uint64_t* coeffs;
-  int nc;
-};
-
-template <int L>
 struct DecideArgs {
   FieldParams<L> F;
-  VEl<L> one;
-  CircProg circ[2];  // arithmetic, sum check
+  Elem<L> one;
+  CircProg circ[2];  // arithmetic, sum check (nc < 0: the check is absent)
   const uint32_t* pair_off;  // the rg_lincheck program (nullptr: no linear check)
   const uint32_t* pairs;
   int n_chk, n_pairs;
@@ -74,43 +59,25 @@ struct DecideArgs {
   int i_lin_mask, i_sum_mask, i_arith_quo, i_lin_quo, i_sum_quo;
 };
 
-template <int L>
-__device__ __forceinline__ void vcp(uint64_t* d, const uint64_t* s) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = s[l];
-}
-template <int L>
-__device__ __forceinline__ void vzero(uint64_t* d) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = 0;
-}
-template <int L>
-__device__ __forceinline__ bool vneq(const uint64_t* a, const uint64_t* b) {
-  uint64_t d = 0;
-#pragma unroll
-  for (int l = 0; l < L; ++l) d |= a[l] ^ b[l];
-  return d != 0;
-}
-
 // The sum of every lane's acc, folded through LDS in a fixed tree (lane i takes i + s for s = 128,
 // 64, ..., 1; canonical f_add, no atomics), left in dst by lane 0.  Called by all lanes.
 template <int L>
 __device__ __forceinline__ void block_sum(uint64_t* red, uint64_t* dst, const uint64_t* acc, const FieldParams<L>& F) {
   const int tid = threadIdx.x;
-  vcp<L>(red + tid * L, acc);
+  el_copy<L>(red + tid * L, acc);
   __syncthreads();
 #pragma unroll 1
   for (int s = kDecideLanes / 2; s > 0; s >>= 1) {
     if (tid < s) {
       uint64_t a[L], b[L];
-      vcp<L>(a, red + tid * L);
-      vcp<L>(b, red + (tid + s) * L);
+      el_copy<L>(a, red + tid * L);
+      el_copy<L>(b, red + (tid + s) * L);
       f_add<L>(a, a, b, F);
-      vcp<L>(red + tid * L, a);
+      el_copy<L>(red + tid * L, a);
     }
     __syncthreads();
   }
-  if (tid == 0) vcp<L>(dst, red);
+  if (tid == 0) el_copy<L>(dst, red);
   __syncthreads();
 }
 
@@ -130,7 +97,7 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
   // clear exponent bit; then its pairs k = tid, tid + 256, ...: the pair's term (verifier.go:276-283)
   // times bc^(n_pairs - k).  Nothing waits here: wave 0 goes on to the constraints meanwhile.
   uint64_t acc_l[L];
-  vzero<L>(acc_l);
+  el_zero<L>(acc_l);
   {
     const int n_pairs = has_l ? a.n_pairs : 0;
     const int special = ((tid & 63) == 0 && tid) ? (tid >> 6) - 1 : -1;  // 0, 1, 2
@@ -144,8 +111,8 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
         e = special == 0 ? a.rank : (special == 1 ? a.shift_exp : 2ull);
       }
       uint64_t r[L], sq[L];
-      vcp<L>(r, a.one.v);  // r = SetUint64(1)
-      vcp<L>(sq, base);
+      el_copy<L>(r, a.one.v);  // r = SetUint64(1)
+      el_copy<L>(sq, base);
 #pragma unroll 1
       for (; e; e >>= 1) {
         if (e & 1) f_mul<L>(r, r, sq, a.F);
@@ -155,18 +122,18 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
         int c = 0;
         while (c + 1 < a.n_chk && (uint32_t)t >= a.pair_off[c + 1]) ++c;  // the pair's checker
         uint64_t term[L], u[L], w[L];
-        vcp<L>(u, a.ev + (size_t)(1 + c) * L);
-        vcp<L>(w, a.evals + (size_t)a.pairs[2 * t + 1] * L);
+        el_copy<L>(u, a.ev + (size_t)(1 + c) * L);
+        el_copy<L>(w, a.evals + (size_t)a.pairs[2 * t + 1] * L);
         f_mul<L>(term, u, w, a.F);  // term.Mul(linCheckTrEval, wIn)
-        vcp<L>(u, a.ev);
-        vcp<L>(w, a.evals + (size_t)a.pairs[2 * t] * L);
+        el_copy<L>(u, a.ev);
+        el_copy<L>(w, a.evals + (size_t)a.pairs[2 * t] * L);
         f_mul<L>(u, u, w, a.F);       // termMul.Mul(linCheckEval, wOut)
         f_sub<L>(term, term, u, a.F);
         f_mul<L>(term, term, r, a.F);
         f_add<L>(acc_l, acc_l, term, a.F);
       } else {
         if (special == 0) f_sub<L>(r, r, a.one.v, a.F);  // vanishEval.Sub(vanishEval, SetUint64(1))
-        vcp<L>(slot + (S_VANISH + special) * L, r);
+        el_copy<L>(slot + (S_VANISH + special) * L, r);
       }
     }
   }
@@ -174,8 +141,8 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
   // ---- evalCircuit on scalars (verifier.go:219-240): the constraints of both lists over lanes, one
   // walk; the common batchConst is applied to the folded sums below
   uint64_t acc_a[L], acc_s[L];
-  vzero<L>(acc_a);
-  vzero<L>(acc_s);
+  el_zero<L>(acc_a);
+  el_zero<L>(acc_s);
   {
     const int nc0 = has_a ? a.circ[0].nc : 0, nc1 = has_s ? a.circ[1].nc : 0;
 #pragma unroll 1
@@ -190,13 +157,13 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
 #pragma unroll 1
       for (uint32_t t = term_off[cc]; t < term_off[cc + 1]; ++t) {
         uint64_t term[L], y[L];
-        vcp<L>(term, coeffs + (size_t)t * L);  // term.Set(c.coeffs[i])
+        el_copy<L>(term, coeffs + (size_t)t * L);  // term.Set(c.coeffs[i])
         const int pi = pw_idx[t];
         const uint32_t k0 = wit_off[t], k1 = wit_off[t + 1];
 #pragma unroll 1
         for (long long k = (pi >= 0) ? (long long)k0 - 1 : (long long)k0; k < (long long)k1; ++k) {
           const uint64_t* src = (k < (long long)k0) ? pw_ev + (size_t)pi * L : a.evals + (size_t)wit[k] * L;
-          vcp<L>(y, src);
+          el_copy<L>(y, src);
           f_mul<L>(term, term, y, a.F);  // term.Mul(term, pwEvals[...]) / term.Mul(term, evals[...])
         }
         if (second) f_add<L>(acc_s, acc_s, term, a.F);  // eval.Add(eval, term); out.Add(out, eval)
@@ -228,13 +195,13 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
       default: if (has_s) p = slot + S_CIRC1 * L, q = slot + S_BC2 * L; break;                // evalCircuit * bc, * bc
     }
     uint64_t u[L], w[L];
-    vzero<L>(u);
+    el_zero<L>(u);
     if (p) {
-      vcp<L>(u, p);
-      vcp<L>(w, q);
+      el_copy<L>(u, p);
+      el_copy<L>(w, q);
       f_mul<L>(u, u, w, a.F);
     }
-    vcp<L>(slot + (S_P0 + tid) * L, u);
+    el_copy<L>(slot + (S_P0 + tid) * L, u);
   }
   __syncthreads();
 
@@ -242,40 +209,40 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
   if (tid < 3) {
     uint64_t s0[L], ev[L], test[L], y[L];
     uint32_t b = 0;
-    vzero<L>(s0);
-    vzero<L>(ev);
-    vzero<L>(test);
+    el_zero<L>(s0);
+    el_zero<L>(ev);
+    el_zero<L>(test);
     if (tid == 0 && has_a) {
-      vcp<L>(ev, slot + S_P0 * L);
-      vcp<L>(test, slot + (S_P0 + 1) * L);
-      b = vneq<L>(ev, test) ? 1u : 0u;  // arithCheck: eval.Cmp(test)
+      el_copy<L>(ev, slot + S_P0 * L);
+      el_copy<L>(test, slot + (S_P0 + 1) * L);
+      b = el_neq<L>(ev, test) ? 1u : 0u;  // arithCheck: eval.Cmp(test)
     }
     if (tid != 0 && (tid == 1 ? has_l : has_s)) {
       const int quo = tid == 1 ? a.i_lin_quo : a.i_sum_quo;
       const int mask = tid == 1 ? a.i_lin_mask : a.i_sum_mask;
       const int p0 = tid == 1 ? S_P0 + 2 : S_P0 + 5;
-      vcp<L>(s0, slot + p0 * L);
-      vcp<L>(y, a.evals + (size_t)(quo + 2) * L);
-      b = vneq<L>(y, s0) ? (tid == 1 ? 2u : 8u) : 0u;  // remHiEval.Cmp(remLoShiftEval)
-      vcp<L>(ev, tid == 1 ? slot + S_LIN * L : slot + (S_P0 + 8) * L);
-      vcp<L>(y, a.evals + (size_t)mask * L);
+      el_copy<L>(s0, slot + p0 * L);
+      el_copy<L>(y, a.evals + (size_t)(quo + 2) * L);
+      b = el_neq<L>(y, s0) ? (tid == 1 ? 2u : 8u) : 0u;  // remHiEval.Cmp(remLoShiftEval)
+      el_copy<L>(ev, tid == 1 ? slot + S_LIN * L : slot + (S_P0 + 8) * L);
+      el_copy<L>(y, a.evals + (size_t)mask * L);
       f_add<L>(ev, ev, y, a.F);  // eval.Add(eval, maskEval)
-      vcp<L>(test, slot + (p0 + 1) * L);
-      vcp<L>(y, slot + (p0 + 2) * L);
+      el_copy<L>(test, slot + (p0 + 1) * L);
+      el_copy<L>(y, slot + (p0 + 2) * L);
       f_add<L>(test, test, y, a.F);  // test.Add(test, rem)
-      vcp<L>(y, a.mask_sums + (size_t)(tid - 1) * L);
+      el_copy<L>(y, a.mask_sums + (size_t)(tid - 1) * L);
       f_add<L>(test, test, y, a.F);  // test.Add(test, maskSum)
-      b |= vneq<L>(ev, test) ? (tid == 1 ? 4u : 16u) : 0u;
+      b |= el_neq<L>(ev, test) ? (tid == 1 ? 4u : 16u) : 0u;
     }
     bits[tid] = b;
     if (a.sides) {
       uint64_t* o = a.sides + (size_t)(tid == 0 ? 0 : (tid == 1 ? 2 : 5)) * L;
       if (tid != 0) {
-        vcp<L>(o, s0);
+        el_copy<L>(o, s0);
         o += L;
       }
-      vcp<L>(o, ev);
-      vcp<L>(o + L, test);
+      el_copy<L>(o, ev);
+      el_copy<L>(o + L, test);
     }
   }
   if (a.pw_out)
@@ -284,28 +251,9 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
   if (tid == 0) a.verdict[0] = (uint64_t)(bits[0] | bits[1] | bits[2]);
 }
 
-static bool bv_same_field(const rg_field* a, const rg_field* b) {
-  return a->L == b->L && memcmp(a->q, b->q, 8 * a->L) == 0;
-}
-
 static rg_status bv_invalid(const std::string& why) {
   set_last_error("buckler verifier: " + why);
   return RG_ERR_INVALID;
-}
-
-static CircProg circ_prog(const rg_circuit* c) {
-  CircProg p;
-  memset(&p, 0, sizeof p);
-  p.nc = -1;
-  if (!c) return p;
-  const char* base = c->prog.as<char>();
-  p.term_off = reinterpret_cast<const uint32_t*>(base);
-  p.pw_idx = reinterpret_cast<const int*>(base + c->off_pw);
-  p.wit_off = reinterpret_cast<const uint32_t*>(base + c->off_wo);
-  p.wit = reinterpret_cast<const uint32_t*>(base + c->off_wi);
-  p.coeffs = reinterpret_cast<const uint64_t*>(base + c->off_cf);
-  p.nc = c->nc;
-  return p;
 }
 
 template <int L>
@@ -315,13 +263,14 @@ static rg_status decide_L(const rg_bverifier* v, const uint64_t* evals, const ui
   const rg_field* f = ntt_field(v->enc);
   DecideArgs<L> a;
   a.F = field_params<L>(f);
-  memcpy(a.one.v, f->one, 8 * L);
+  a.one = elem<L>(f->one);
   a.circ[0] = circ_prog(v->arith);
   a.circ[1] = circ_prog(v->sum);
-  a.pair_off = v->lin ? v->lin->prog.as<uint32_t>() : nullptr;
-  a.n_chk = v->lin ? (int)v->lin->chk.size() : 0;
-  a.pairs = v->lin ? a.pair_off + a.n_chk + 1 : nullptr;
-  a.n_pairs = v->lin ? v->lin->n_pairs : 0;
+  const LinProg lp = lin_prog(v->lin);
+  a.pair_off = lp.pair_off;
+  a.pairs = lp.pairs;
+  a.n_chk = lp.n_chk;
+  a.n_pairs = lp.n_pairs;
   a.evals = evals;
   a.ev = ev;
   a.chal = chal;
@@ -361,7 +310,7 @@ rg_status rg_buckler_verifier_create(const rg_ntt* enc_plan, size_t jindo_rank, 
   if (!lin && !arith && !sum) return bv_invalid("no check: lin, arith and sum are all NULL");
   const rg_field* f = ntt_field(enc_plan);
   const long long rank = rg_ntt_rank(enc_plan);
-  if (f->L != 1 && f->L != 2 && f->L != 4 && f->L != 7 && f->L != 14) {
+  if (!limbs_supported(f->L)) {
     set_last_error("buckler verifier: no kernel for " + std::to_string(f->L) + " limbs (1, 2, 4, 7, 14)");
     return RG_ERR_UNSUPPORTED;
   }
@@ -369,14 +318,14 @@ rg_status rg_buckler_verifier_create(const rg_ntt* enc_plan, size_t jindo_rank, 
     return bv_invalid("jindo_rank " + std::to_string(jindo_rank) + " < rank - 1 or out of range");
   if (w_cnt > ((size_t)1 << 30) || n_pw > ((size_t)1 << 20)) return bv_invalid("w_cnt or n_pw out of range");
   if (lin) {
-    if (rg_ntt_rank(lin->enc) != rank || !bv_same_field(f, ntt_field(lin->enc)))
+    if (rg_ntt_rank(lin->enc) != rank || !same_field(f, ntt_field(lin->enc)))
       return bv_invalid("the linear check's encoder plan has another rank or field");
     if (lin->max_w >= (long long)w_cnt) return bv_invalid("a pair index >= w_cnt");
   }
   const rg_circuit* cs[2] = {arith, sum};
   for (const rg_circuit* c : cs) {
     if (!c) continue;
-    if (!bv_same_field(f, &c->f)) return bv_invalid("a circuit of another field");
+    if (!same_field(f, &c->f)) return bv_invalid("a circuit of another field");
     if (c->max_w >= (long long)w_cnt) return bv_invalid("a circuit's witness index >= w_cnt");
     if (c->max_pw >= (long long)n_pw) return bv_invalid("a circuit's public-witness index >= n_pw");
   }
@@ -470,9 +419,9 @@ rg_status rg_buckler_verify_checks(const rg_bverifier* v, const uint64_t* evals,
   RG_TRY(rg_buckler_verify_checks_dev(v, dev.as<uint64_t>(), dpw.as<uint64_t>(), dch.as<uint64_t>(),
                                       dms.as<uint64_t>(), dvd.as<uint64_t>(), dsd.as<uint64_t>(), dpe.as<uint64_t>(),
                                       dscr.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(verdict, dvd.p, 8, hipMemcpyDeviceToHost));
-  if (sides) RG_HIP(hipMemcpy(sides, dsd.p, 8 * e, hipMemcpyDeviceToHost));
-  if (dpe.p) RG_HIP(hipMemcpy(pw_evals, dpe.p, v->n_pw * e, hipMemcpyDeviceToHost));
+  RG_TRY(dvd.download(verdict, 8));
+  if (sides) RG_TRY(dsd.download(sides, 8 * e));
+  if (dpe.p) RG_TRY(dpe.download(pw_evals, v->n_pw * e));
   return RG_OK;
 }
 

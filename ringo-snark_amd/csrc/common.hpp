@@ -1,5 +1,7 @@
 // common.hpp -- shared host-side plumbing of libringo: status codes, HIP error capture,
-// device buffers, and the opaque handle definitions behind include/ringo.h.
+// device buffers, the launch and field-check helpers of every unit (grid256, elem, is_pow2,
+// same_field, dispatch_limbs / limbs_supported), and the opaque handle definitions behind
+// include/ringo.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -93,6 +95,10 @@ struct DevBuf {
     RG_HIP(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
     return RG_OK;
   }
+  rg_status download(void* dst, size_t n) const {  // the buffer's first n bytes (a blocking copy)
+    RG_HIP(hipMemcpy(dst, p, n, hipMemcpyDeviceToHost));
+    return RG_OK;
+  }
   template <class T>
   T* as() const {
     return reinterpret_cast<T*>(p);
@@ -100,6 +106,19 @@ struct DevBuf {
 };
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// blocks of 256 lanes that cover n items
+inline unsigned grid256(long long n) { return (unsigned)((n + 255) / 256); }
+
+inline bool is_pow2(long long n) { return n > 0 && (n & (n - 1)) == 0; }
+
+// an element of L words as a kernel argument
+template <int L>
+inline Elem<L> elem(const uint64_t* x) {
+  Elem<L> e;
+  el_copy<L>(e.v, x);
+  return e;
+}
 
 // Compile-time loop: f(std::integral_constant<int, i>) for i in [0, N), so a body indexes its
 // register arrays with constants (a rolled loop the unroller leaves alone indexes them dynamically)
@@ -168,6 +187,14 @@ inline rg_status dispatch_limbs(int L, F&& f) {
     case 14: return f(std::integral_constant<int, 14>{});
     default: return RG_ERR_UNSUPPORTED;
   }
+}
+// "is this limb count built?", read off that switch
+inline bool limbs_supported(int L) {
+  return dispatch_limbs(L, [](auto) { return RG_OK; }) == RG_OK;
+}
+
+inline bool same_field(const rg_field* a, const rg_field* b) {
+  return a->L == b->L && memcmp(a->q, b->q, 8 * a->L) == 0;
 }
 
 }  // namespace rg

@@ -252,10 +252,29 @@ RG_HD void f_mul(uint64_t* z, const uint64_t* x, const uint64_t* y, const FieldP
   for (int i = 0; i < L; ++i) z[i] = use_s ? s[i] : t[i];
 }
 
-// Element container (registers)
+// Element container (registers, and the by-value form of an element in kernel arguments)
 template <int L>
 struct Elem {
   uint64_t v[L];
 };
+
+// The plain element moves every unit shares: d = s, d = 0, a != b
+template <int L>
+RG_HD void el_copy(uint64_t* d, const uint64_t* s) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) d[l] = s[l];
+}
+template <int L>
+RG_HD void el_zero(uint64_t* d) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) d[l] = 0;
+}
+template <int L>
+RG_HD bool el_neq(const uint64_t* a, const uint64_t* b) {
+  uint64_t d = 0;
+#pragma unroll
+  for (int l = 0; l < L; ++l) d |= a[l] ^ b[l];
+  return d != 0;
+}
 
 }  // namespace rg

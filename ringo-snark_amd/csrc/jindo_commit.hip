@@ -114,12 +114,10 @@ __global__ __launch_bounds__(256) void digits_kernel(DigitArgs<L> a) {
   bool have = true;
   if (col == S.cols) {  // mask column: every slot present
     const uint64_t* m = a.mask + ((b * S.rows + row) * S.slots + slot) * L;
-#pragma unroll
-    for (int l = 0; l < L; ++l) x[l] = m[l];
+    el_copy<L>(x, m);
   } else if (row == S.rows - 1) {  // last row
     const uint64_t* m = a.last_row + (b * cs + (long long)col * S.slots + slot) * L;
-#pragma unroll
-    for (int l = 0; l < L; ++l) x[l] = m[l];
+    el_copy<L>(x, m);
   } else if (row == 0) {  // first row: v[i] - lastRow[i-1] (genFirstLastRow :74-83)
     const long long i = (long long)col * S.slots + slot;
     uint64_t vi[L], lr[L];
@@ -130,8 +128,7 @@ __global__ __launch_bounds__(256) void digits_kernel(DigitArgs<L> a) {
       for (int l = 0; l < L; ++l) x[l] = vi[l];
     } else {
       const uint64_t* m = a.last_row + (b * cs + i - 1) * L;
-#pragma unroll
-      for (int l = 0; l < L; ++l) lr[l] = m[l];
+      el_copy<L>(lr, m);
       f_sub<L>(x, vi, lr, a.F);
     }
   } else {  // data row: v[row*cs + col*slots + slot] when < nv
@@ -577,7 +574,7 @@ template <int JB, bool WIDE>
 static rg_status launch_mac_jb(const MacArgs& m, int j0, hipStream_t st) {
   const long long groups = (m.ncols + kMacNC - 1) / kMacNC;
   const long long threads = groups * m.nl * m.d;
-  hipLaunchKernelGGL((mac_kernel<JB, kMacNC, WIDE>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, m, j0);
+  hipLaunchKernelGGL((mac_kernel<JB, kMacNC, WIDE>), dim3(grid256(threads)), dim3(256), 0, st, m, j0);
   return check_launch("jindo mac");
 }
 
@@ -838,10 +835,9 @@ static rg_status launch_digits(const rg_jindo* J, size_t batch, const uint64_t* 
   a.d_slots = make_idxdiv((uint32_t)J->p.slots);
   a.d_rows = make_idxdiv((uint32_t)J->p.rows);
   a.d_cols1 = make_idxdiv((uint32_t)(J->p.cols + 1));
-  const long long blocks = (a.total + 255) / 256;
   if (J->p.slots * J->p.exp < J->p.d)  // the coefficients no thread writes read as zero digits (baseEncodeTo)
     RG_HIP(hipMemsetAsync(digits, 0, sizes_of(J->p, batch).digits, st));
-  hipLaunchKernelGGL(digits_kernel<L>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(digits_kernel<L>, dim3(grid256(a.total)), dim3(256), 0, st, a);
   return check_launch("jindo digits");
 }
 

@@ -770,8 +770,7 @@ __global__ __launch_bounds__(512) void uniform_elems_kernel(UniArgs<L> a) {
   }
   uint64_t* dst = i < nl ? a.last_row + (b * nl + i) * L : a.mask + (b * (per - nl) + (i - nl)) * L;
   if (i == nl - 1) {
-#pragma unroll
-    for (int l = 0; l < L; ++l) dst[l] = 0;
+    el_zero<L>(dst);
     return;
   }
   const unsigned long long inst = (a.first_commit + (unsigned long long)b) * (unsigned long long)per + (unsigned long long)i;
@@ -788,8 +787,7 @@ __global__ __launch_bounds__(512) void uniform_elems_kernel(UniArgs<L> a) {
       }
       z[L - 1] &= topm;  // the last byte's unused top bits (element.go:320-325)
       if (!geq_q<L>(z, a.F)) {
-#pragma unroll
-        for (int l = 0; l < L; ++l) dst[l] = z[l];
+        el_copy<L>(dst, z);
         return;
       }
     }
@@ -800,8 +798,7 @@ __global__ __launch_bounds__(512) void uniform_elems_kernel(UniArgs<L> a) {
   int left = 0;  // unread bytes of `word`
   for (;;) {
     uint64_t z[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) z[l] = 0;
+    el_zero<L>(z);
     for (int j = 0; j < a.kbytes; ++j) {
       if (!left) {
         word = u.sample();
@@ -816,8 +813,7 @@ __global__ __launch_bounds__(512) void uniform_elems_kernel(UniArgs<L> a) {
         if ((j >> 3) == l) z[l] |= byte << (8 * (j & 7));
     }
     if (!geq_q<L>(z, a.F)) {
-#pragma unroll
-      for (int l = 0; l < L; ++l) dst[l] = z[l];
+      el_copy<L>(dst, z);
       return;
     }
   }
@@ -864,8 +860,7 @@ __global__ __launch_bounds__(512) void uniform_whole_kernel(UniArgs<L> a, int* f
         t = 0;
         return;
       }
-#pragma unroll
-      for (int l = 0; l < L; ++l) dst[l] = 0;  // genFirstLastRow leaves it zero
+      el_zero<L>(dst);  // genFirstLastRow leaves it zero
       gid += stride;
     }
   };
@@ -938,8 +933,7 @@ __global__ __launch_bounds__(512) void uniform_fix_kernel(UniArgs<L> a, const in
       }
       z[L - 1] &= topm;
       if (!geq_q<L>(z, a.F)) {
-#pragma unroll
-        for (int l = 0; l < L; ++l) dst[l] = z[l];
+        el_copy<L>(dst, z);
         break;
       }
     }

@@ -167,8 +167,7 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<L> a) {
       f_add<L>(v, v, t, a.F);
     }
     if (neg) f_neg<L>(v, v, a.F);
-#pragma unroll
-    for (int j = 0; j < L; ++j) ce[(long long)k * L + j] = v[j];
+    el_copy<L>(ce + (long long)k * L, v);
   }
   __syncthreads();
   for (int i = tid; i < a.nout; i += blockDim.x) {  // Horner over j = exp-1 .. 0
@@ -179,8 +178,7 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<L> a) {
       f_mul<L>(v, v, a.bmont, a.F);
       f_add<L>(v, v, ce + (long long)(j * a.slots + i) * L, a.F);
     }
-#pragma unroll
-    for (int j = 0; j < L; ++j) a.out[(pid * a.nout + i) * L + j] = v[j];
+    el_copy<L>(a.out + (pid * a.nout + i) * L, v);
   }
 }
 
@@ -201,8 +199,7 @@ __global__ __launch_bounds__(256) void dot2_kernel(FieldParams<L> F, const uint6
       f_mul<L>(t, x + i * L, y + i * L, F);
       f_add<L>(acc, acc, t, F);
     }
-#pragma unroll
-    for (int j = 0; j < L; ++j) red[threadIdx.x * L + j] = acc[j];
+    el_copy<L>(red + threadIdx.x * L, acc);
     __syncthreads();
     for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
       if ((int)threadIdx.x < s) f_add<L>(red + threadIdx.x * L, red + threadIdx.x * L, red + (threadIdx.x + s) * L, F);
@@ -357,8 +354,7 @@ __global__ __launch_bounds__(256) void encode_left_kernel(PointArgs<L> a) {
     // left[rows - 1] = x is written last (utils.go:70), also when skip^(rows-1) was there
     const uint64_t* e = row == a.rows - 1 ? a.x : a.lp + (long long)row * L;
     uint64_t xv[L], c[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) xv[l] = e[l];
+    el_copy<L>(xv, e);
     f_redc<L>(c, xv, a.F);  // Slice = fromMont
     auto put = [&](int j, uint32_t dg) {  // MForm(digit) at coefficient j * slots (digit < 2^32 <= any word)
       for (int l = 0; l < nl; ++l) {
@@ -575,7 +571,7 @@ static rg_status launch_combine(const RnsPrime* P, int nl, int d, int cut, const
     c[l] = (uint64_t)x;
   }
   const long long n = npoly * nl * d;
-  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, B, out, n, nl, d, R, c[0],
+  hipLaunchKernelGGL(combine_kernel, dim3(grid256(n)), dim3(256), 0, st, A, B, out, n, nl, d, R, c[0],
                      c[1], c[2], c[3]);
   return check_launch("jindo combine");
 }
@@ -707,7 +703,7 @@ rg_status rg_jindo_verify_dev(const rg_jindo* J, size_t batch, const uint64_t* d
     RG_TRY(launch_mac(m, st));
   }
   RG_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-  hipLaunchKernelGGL(neq_kernel, dim3((unsigned)((pq + 255) / 256)), dim3(256), 0, st, p1.as<uint64_t>(),
+  hipLaunchKernelGGL(neq_kernel, dim3(grid256(pq)), dim3(256), 0, st, p1.as<uint64_t>(),
                      p2.as<uint64_t>(), pq, flag.as<int>());
   RG_TRY(check_launch("jindo consistency"));
   // verifyEval (:224-259): sum_{i,j} right[i slots + j] * Decode(pfInv.Partial[i])[j] ==
@@ -838,7 +834,7 @@ rg_status rg_jindo_eval_reduce_dev(const rg_jindo* J, uint64_t* d_ob_incom, uint
   const RingDev rq = ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b), ro = ring_dev(J->ro, p.nqo, J->rootso_f, J->rootso_b);
   auto go = [&](uint64_t* x, long long npoly, int nl, const RingDev& R) {
     const long long n = npoly * nl * p.d;
-    hipLaunchKernelGGL(rns_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, npoly, nl, p.d, R);
+    hipLaunchKernelGGL(rns_reduce_kernel, dim3(grid256(n)), dim3(256), 0, st, x, npoly, nl, p.d, R);
     return check_launch("jindo eval reduce");
   };
   RG_TRY(go(d_ob_incom, p.dcmp, p.nqo, ro));

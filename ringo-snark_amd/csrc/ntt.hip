@@ -19,7 +19,6 @@ namespace rg {
 // must match ntt_kernels.hpp (RadixOf + 8, kMinTiledP)
 static int pmax_of(int L) { return (L <= 2 ? 4 : 3) + 8; }
 static const int kMinTiledP = 6;
-static bool supported_L(int L) { return L == 1 || L == 2 || L == 4 || L == 7 || L == 14; }
 }  // namespace rg
 
 struct rg_ntt {
@@ -322,7 +321,7 @@ rg_status rg_ntt_create(const rg_field* f, int rank, int negacyclic, rg_ntt** ou
   if (!f || !out) return RG_ERR_INVALID;
   *out = nullptr;
   RG_TRY(check_rank(f, rank));
-  if (!supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  if (!limbs_supported(f->L)) return RG_ERR_UNSUPPORTED;
   rg_ntt* t = new_plan(f, rank, negacyclic);
   rg_status s = build_tables(t);
   if (s == RG_OK) s = finalize(t);
@@ -339,7 +338,7 @@ rg_status rg_ntt_create_from_tables(const rg_field* f, int rank, int negacyclic,
   if (!f || !out || !tw || !tw_inv || !rank_inv) return RG_ERR_INVALID;
   *out = nullptr;
   RG_TRY(check_rank(f, rank));
-  if (!supported_L(f->L)) return RG_ERR_UNSUPPORTED;
+  if (!limbs_supported(f->L)) return RG_ERR_UNSUPPORTED;
   const int L = f->L;
   rg_ntt* t = new_plan(f, rank, negacyclic);
   t->h_tw.assign(tw, tw + (size_t)rank * L);

@@ -14,8 +14,6 @@
 // Every sum is the canonical arithmetic of field.hpp and the value of a polynomial at a point is
 // one residue, so every output limb equals the reference's single Horner pass.  No atomics: a
 // tile sum has one writer (lane 0 of its workgroup), an output element one lane.
-#include <cstring>
-
 #include "common.hpp"
 #include "field.hpp"
 
@@ -27,12 +25,6 @@ constexpr int kEvalTile = kEvalLanes * kEvalK;    // T: coefficients per workgro
 // loads in flight per lane ahead of their Horner steps (their registers: U L words)
 template <int L>
 constexpr int kEvalUnroll = L <= 4 ? 4 : (L <= 7 ? 2 : 1);
-
-template <int L>
-__device__ __forceinline__ void ecp(uint64_t* d, const uint64_t* s) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = s[l];
-}
 
 // pw: x^t for t <= 256 ([257][L]); tiles [batch][ntiles][L]
 template <int L>
@@ -47,7 +39,7 @@ __global__ __launch_bounds__(kEvalLanes) void eval_tile_kernel(FieldParams<L> F,
   const long long left = n - lo;  // >= 1: coefficients of this tile and after
   const uint64_t* src = p + (b * stride + lo) * L;
   uint64_t y[L], z[L];
-  ecp<L>(y, pw + (long long)kEvalLanes * L);
+  el_copy<L>(y, pw + (long long)kEvalLanes * L);
 #pragma unroll
   for (int l = 0; l < L; ++l) z[l] = 0;
   // rows 256 k .. 256 k + 255 that hold a coefficient below n (uniform over the workgroup)
@@ -79,10 +71,10 @@ __global__ __launch_bounds__(kEvalLanes) void eval_tile_kernel(FieldParams<L> F,
   }
   {
     uint64_t xt[L];
-    ecp<L>(xt, pw + (long long)t * L);
+    el_copy<L>(xt, pw + (long long)t * L);
     f_mul<L>(z, z, xt, F);
   }
-  ecp<L>(red + t * L, z);
+  el_copy<L>(red + t * L, z);
   __syncthreads();
   for (int s = kEvalLanes >> 1; s > 0; s >>= 1) {
     if (t < s) f_add<L>(red + t * L, red + t * L, red + (t + s) * L, F);
@@ -100,14 +92,14 @@ __global__ __launch_bounds__(256) void eval_fold_kernel(FieldParams<L> F, const 
   uint64_t y[L], z[L];
 #pragma unroll
   for (int l = 0; l < L; ++l) y[l] = z[l] = 0;
-  if (ntiles) ecp<L>(y, xT);
+  if (ntiles) el_copy<L>(y, xT);
   for (long long j = ntiles - 1; j >= 0; --j) {
     uint64_t c[L];
-    ecp<L>(c, tiles + (b * ntiles + j) * L);
+    el_copy<L>(c, tiles + (b * ntiles + j) * L);
     f_mul<L>(z, z, y, F);
     f_add<L>(z, z, c, F);
   }
-  ecp<L>(out + b * L, z);
+  el_copy<L>(out + b * L, z);
 }
 
 static long long eval_tiles(size_t n) { return (long long)((n + kEvalTile - 1) / kEvalTile); }
@@ -127,12 +119,10 @@ static rg_status eval_batch_L(const rg_field* f, const uint64_t* p, long long n,
                        ntiles, pw, tiles);
     RG_TRY(check_launch("evaluate batch tiles"));
   }
-  hipLaunchKernelGGL(eval_fold_kernel<L>, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, F, tiles, ntiles,
+  hipLaunchKernelGGL(eval_fold_kernel<L>, dim3(grid256(batch)), dim3(256), 0, st, F, tiles, ntiles,
                      batch, pt + kEvalK * L, out);
   return check_launch("evaluate batch fold");
 }
-
-static bool eval_limbs_ok(int L) { return L == 1 || L == 2 || L == 4 || L == 7 || L == 14; }
 
 // the checks both forms share, before any device call; *done: nothing to launch
 static rg_status eval_batch_check(const rg_field* f, const void* p, size_t n, size_t stride, size_t batch,
@@ -142,7 +132,7 @@ static rg_status eval_batch_check(const rg_field* f, const void* p, size_t n, si
     set_last_error("evaluate batch: NULL field handle");
     return RG_ERR_INVALID;
   }
-  if (!eval_limbs_ok(f->L)) {
+  if (!limbs_supported(f->L)) {
     set_last_error("evaluate batch: no kernel for " + std::to_string(f->L) + " limbs (1, 2, 4, 7, 14)");
     return RG_ERR_UNSUPPORTED;
   }
@@ -208,8 +198,7 @@ rg_status rg_poly_evaluate_batch(const rg_field* f, const uint64_t* p, size_t n,
   RG_TRY(ds.alloc(rg_poly_evaluate_batch_scratch_bytes(f, n, batch)));
   RG_TRY(rg_poly_evaluate_batch_dev(f, n ? dp.as<uint64_t>() : nullptr, n, stride, batch, dx.as<uint64_t>(),
                                     dout.as<uint64_t>(), ds.p, nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, batch * e, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, batch * e);
 }
 
 }  // extern "C"

@@ -33,12 +33,6 @@ struct PolyArgs {
   int logn;
 };
 
-template <int L>
-__device__ __forceinline__ void cp(uint64_t* d, const uint64_t* s) {
-#pragma unroll
-  for (int l = 0; l < L; ++l) d[l] = s[l];
-}
-
 // ---- QuoRemByVanishing ----------------------------------------------------------------------
 template <int L>
 __global__ __launch_bounds__(256) void quorem_kernel(PolyArgs<L> a) {
@@ -55,20 +49,20 @@ __global__ __launch_bounds__(256) void quorem_kernel(PolyArgs<L> a) {
   const long long top = (N - 1 - k) / M;  // largest t with k + tM < N
   for (long long t = top; t >= 1; --t) {
     uint64_t x[L];
-    cp<L>(x, p + (k + t * M) * L);
+    el_copy<L>(x, p + (k + t * M) * L);
     f_add<L>(s, s, x, a.F);
-    cp<L>(quo + (k + (t - 1) * M) * L, s);
+    el_copy<L>(quo + (k + (t - 1) * M) * L, s);
     uint64_t z[L] = {0};
-    cp<L>(rem + (k + t * M) * L, z);
+    el_copy<L>(rem + (k + t * M) * L, z);
   }
   {  // the class's last quotient slot k + top M (>= N - M) receives nothing: zero
     uint64_t z[L] = {0};
-    cp<L>(quo + (k + top * M) * L, z);
+    el_copy<L>(quo + (k + top * M) * L, z);
   }
   uint64_t x[L];
-  cp<L>(x, p + k * L);
+  el_copy<L>(x, p + k * L);
   f_add<L>(x, x, s, a.F);
-  cp<L>(rem + k * L, x);
+  el_copy<L>(rem + k * L, x);
 }
 
 // M >= rank: quotient 0, remainder p (the reference's loop does not run)
@@ -89,13 +83,13 @@ __global__ __launch_bounds__(256) void aut_coeff_kernel(PolyArgs<L> a) {
   const long long b = gid / N, i = gid % N;
   const long long j = (long long)(((unsigned long long)i * (unsigned long long)a.m) % (unsigned long long)(2 * N));
   uint64_t x[L];
-  cp<L>(x, a.in + (b * N + i) * L);
+  el_copy<L>(x, a.in + (b * N + i) * L);
   if (j < N) {
-    cp<L>(a.out + (b * N + j) * L, x);
+    el_copy<L>(a.out + (b * N + j) * L, x);
   } else {
     uint64_t y[L];
     f_neg<L>(y, x, a.F);
-    cp<L>(a.out + (b * N + j - N) * L, y);
+    el_copy<L>(a.out + (b * N + j - N) * L, y);
   }
 }
 
@@ -111,7 +105,7 @@ __global__ __launch_bounds__(256) void aut_ntt_kernel(PolyArgs<L> a) {
   const long long b = gid / N, k = gid % N;
   const long long i = brv_n(k, a.logn);
   const long long j = (long long)((((unsigned long long)(2 * i + 1) * (unsigned long long)a.m) % (unsigned long long)(2 * N) - 1) >> 1);
-  cp<L>(a.out + (b * N + k) * L, a.in + (b * N + brv_n(j, a.logn)) * L);
+  el_copy<L>(a.out + (b * N + k) * L, a.in + (b * N + brv_n(j, a.logn)) * L);
 }
 
 // ---- Evaluate -------------------------------------------------------------------------------
@@ -125,15 +119,15 @@ __global__ __launch_bounds__(256) void eval_level_kernel(FieldParams<L> F, const
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= (n + kEvalChunk - 1) / kEvalChunk) return;
   uint64_t yv[L], z[L] = {0};
-  cp<L>(yv, y);
+  el_copy<L>(yv, y);
   const long long lo = c * kEvalChunk, hi = min(n, lo + kEvalChunk);
   for (long long i = hi - 1; i >= lo; --i) {
     uint64_t t[L], pi[L];
     f_mul<L>(t, z, yv, F);
-    cp<L>(pi, in + i * L);
+    el_copy<L>(pi, in + i * L);
     f_add<L>(z, t, pi, F);
   }
-  cp<L>(out + c * L, z);
+  el_copy<L>(out + c * L, z);
 }
 
 // y' = y^64 (six squarings), one lane
@@ -141,9 +135,9 @@ template <int L>
 __global__ void eval_pow_kernel(FieldParams<L> F, const uint64_t* y, uint64_t* out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   uint64_t v[L];
-  cp<L>(v, y);
+  el_copy<L>(v, y);
   for (int s = 0; s < 6; ++s) f_mul<L>(v, v, v, F);
-  cp<L>(out, v);
+  el_copy<L>(out, v);
 }
 
 template <int L>
@@ -153,8 +147,6 @@ static PolyArgs<L> args_of(const rg_field* f) {
   a.F = field_params<L>(f);
   return a;
 }
-
-static unsigned grid_of(long long n) { return (unsigned)((n + 255) / 256); }
 
 template <int L>
 static rg_status quorem_L(const rg_field* f, long long rank, long long m, uint64_t* quo, uint64_t* rem,
@@ -167,9 +159,9 @@ static rg_status quorem_L(const rg_field* f, long long rank, long long m, uint64
   a.batch = batch;
   a.m = m;
   if (m >= rank)
-    hipLaunchKernelGGL(quorem_trivial_kernel<L>, dim3(grid_of(batch * rank * L)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(quorem_trivial_kernel<L>, dim3(grid256(batch * rank * L)), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(quorem_kernel<L>, dim3(grid_of(batch * m)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(quorem_kernel<L>, dim3(grid256(batch * m)), dim3(256), 0, st, a);
   return check_launch("quorem");
 }
 
@@ -184,9 +176,9 @@ static rg_status aut_L(const rg_field* f, long long rank, long long idx, bool nt
   a.m = idx;
   while ((1LL << a.logn) < rank) ++a.logn;
   if (ntt)
-    hipLaunchKernelGGL(aut_ntt_kernel<L>, dim3(grid_of(batch * rank)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(aut_ntt_kernel<L>, dim3(grid256(batch * rank)), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(aut_coeff_kernel<L>, dim3(grid_of(batch * rank)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(aut_coeff_kernel<L>, dim3(grid256(batch * rank)), dim3(256), 0, st, a);
   return check_launch("aut");
 }
 
@@ -205,7 +197,7 @@ static rg_status eval_L(const rg_field* f, const uint64_t* p, long long n, const
   for (;;) {
     const long long m = (cur + kEvalChunk - 1) / kEvalChunk;
     uint64_t* dst = m == 1 ? out : buf[lvl & 1];
-    hipLaunchKernelGGL(eval_level_kernel<L>, dim3(grid_of(m)), dim3(256), 0, st, a.F, src, cur, y, dst);
+    hipLaunchKernelGGL(eval_level_kernel<L>, dim3(grid256(m)), dim3(256), 0, st, a.F, src, cur, y, dst);
     RG_TRY(check_launch("evaluate level"));
     if (m == 1) return RG_OK;
     hipLaunchKernelGGL(eval_pow_kernel<L>, dim3(1), dim3(64), 0, st, a.F, y, pw[lvl & 1]);
@@ -372,15 +364,13 @@ __global__ __launch_bounds__(256) void modswitch_kernel(MsArgs<L> a) {
   for (int j = 0; j < L; ++j) nz |= r[j] != 0;
   if (neg && nz) {  // (-M) mod q = q - (M mod q)
     uint64_t t[L];
-#pragma unroll
-    for (int j = 0; j < L; ++j) t[j] = a.F.q[j];
+    el_copy<L>(t, a.F.q);
     mw_sub(t, r, L);
-#pragma unroll
-    for (int j = 0; j < L; ++j) r[j] = t[j];
+    el_copy<L>(r, t);
   }
   uint64_t o[L];
   f_mul<L>(o, r, a.r2, a.F);  // SetBigInt: r R mod q
-  cp<L>(a.out + gid * L, o);
+  el_copy<L>(a.out + gid * L, o);
 }
 
 // host: floor(2^(64 nx) / m) by restoring binary division (m: nm words, result <= nx + 1 words)
@@ -448,11 +438,9 @@ static rg_status modswitch_L(const rg_field* f, const uint64_t* pbig, int w, con
   a.nmu1 = host_recip(qbig, nqb, a.nx, a.mu1, kMsMaxW + 16);
   a.nmu2 = host_recip(f->q, L, a.nx, a.mu2, kMsMaxW + 16);
   if (a.nmu1 < 0 || a.nmu2 < 0) return RG_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(modswitch_kernel<L>, dim3(grid_of(n)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(modswitch_kernel<L>, dim3(grid256(n)), dim3(256), 0, st, a);
   return check_launch("modswitch");
 }
-
-static bool pow2(long long n) { return n > 0 && !(n & (n - 1)); }
 
 }  // namespace rg
 
@@ -479,7 +467,7 @@ rg_status rg_poly_quorem_vanishing_dev(const rg_field* f, size_t rank, long long
 rg_status rg_poly_aut_dev(const rg_field* f, size_t rank, long long idx, int ntt_domain, uint64_t* d_out,
                           const uint64_t* d_p, size_t batch, void* stream) {
   if (!f || (batch && (!d_out || !d_p)) || d_out == d_p) return RG_ERR_INVALID;
-  if (!pow2((long long)rank)) return RG_ERR_INVALID;
+  if (!is_pow2((long long)rank)) return RG_ERR_INVALID;
   if ((idx & 1) == 0) return RG_ERR_INVALID;  // cyclotomic.go:34-36 "AutTo: idx must be odd"
   if (batch == 0) return RG_OK;
   const long long n2 = 2 * (long long)rank;
@@ -529,9 +517,8 @@ rg_status rg_poly_quorem_vanishing(const rg_field* f, size_t rank, long long n_v
   RG_TRY(dr.alloc(bytes));
   RG_TRY(rg_poly_quorem_vanishing_dev(f, rank, n_vanish, dq.as<uint64_t>(), dr.as<uint64_t>(), dp.as<uint64_t>(), 1,
                                       nullptr));
-  RG_HIP(hipMemcpy(quo, dq.p, bytes, hipMemcpyDeviceToHost));
-  RG_HIP(hipMemcpy(rem, dr.p, bytes, hipMemcpyDeviceToHost));
-  return RG_OK;
+  RG_TRY(dq.download(quo, bytes));
+  return dr.download(rem, bytes);
 }
 
 rg_status rg_poly_aut(const rg_field* f, size_t rank, long long idx, int ntt_domain, uint64_t* out, const uint64_t* p) {
@@ -541,8 +528,7 @@ rg_status rg_poly_aut(const rg_field* f, size_t rank, long long idx, int ntt_dom
   RG_TRY(dp.upload(p, bytes));
   RG_TRY(dq.alloc(bytes));
   RG_TRY(rg_poly_aut_dev(f, rank, idx, ntt_domain, dq.as<uint64_t>(), dp.as<uint64_t>(), 1, nullptr));
-  RG_HIP(hipMemcpy(out, dq.p, bytes, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dq.download(out, bytes);
 }
 
 rg_status rg_poly_modswitch(const rg_field* f, size_t n, const uint64_t* pbig, size_t w, const uint64_t* qbig,
@@ -553,8 +539,7 @@ rg_status rg_poly_modswitch(const rg_field* f, size_t n, const uint64_t* pbig, s
   RG_TRY(dp.upload(pbig, n * w * 8));
   RG_TRY(dq.alloc(n * f->L * 8));
   RG_TRY(rg_poly_modswitch_dev(f, n, dp.as<uint64_t>(), w, qbig, dq.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dq.p, n * f->L * 8, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dq.download(out, n * f->L * 8);
 }
 
 rg_status rg_poly_evaluate(const rg_field* f, const uint64_t* p, size_t n, const uint64_t* x, uint64_t* out) {
@@ -566,8 +551,7 @@ rg_status rg_poly_evaluate(const rg_field* f, const uint64_t* p, size_t n, const
   RG_TRY(ds.alloc(rg_poly_evaluate_scratch_bytes(f, n) + 8));
   RG_TRY(rg_poly_evaluate_dev(f, n ? dp.as<uint64_t>() : nullptr, n, dx.as<uint64_t>(), dout.as<uint64_t>(),
                               ds.as<uint64_t>(), nullptr));
-  RG_HIP(hipMemcpy(out, dout.p, f->L * 8, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return dout.download(out, f->L * 8);
 }
 
 }  // extern "C"
