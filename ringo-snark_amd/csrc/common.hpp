@@ -23,7 +23,9 @@ void set_last_error(const std::string& msg);
 // Measurement / A-B switches.  libringo.so links knobs.hip, where every knob is unset (nullptr:
 // the production choice) and the probe is 0.  Only the experiments build, libringo_exp.so
 // (tools/experiments/knobs_env.hip), reads them from the RINGO_* environment and honours
-// rg_set_probe; the production library has no environment access at all.
+// rg_set_probe; the production library has no environment access at all.  The two NTT knobs are
+// read when a plan is created (ntt.hip finalize()) and hold for the plan's life; the probe is read
+// by every call.
 enum class Knob : int {
   NttKernel,   // RINGO_NTT_KERNEL   r*: generic single-word / q255 pass kernels; stage: wide fields per stage
   NttChunkMb,  // RINGO_NTT_CHUNK_MB polys per pass pair bounded to this many MiB

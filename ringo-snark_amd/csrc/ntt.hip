@@ -1,8 +1,11 @@
 // ntt.hip -- host side of the bigpoly transformers: table construction (the reference's
-// generator search and layouts, math/bigpoly/ntt.go:26-95,153-203), pass planning, and the
-// C ABI (include/ringo.h).  Kernels: ntt_kernels.hpp, instantiated per limb count in
-// ntt_l1.hip / ntt_l2.hip / ntt_l4.hip / ntt_lwide.hip.
+// generator search and layouts, math/bigpoly/ntt.go:26-95,153-203), plan creation and the C ABI
+// (include/ringo.h).  A plan picks its kernels when it is created: finalize() asks ntt_route.hpp
+// for each direction's route and passes, reads the experiments build's NttKernel / NttChunkMb
+// switches (here and nowhere else), uploads the table format those routes read and creates the
+// helper stream if they use one; run() switches on the stored route.  Runners: ntt_plan.hpp.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -11,28 +14,16 @@
 #include "common.hpp"
 #include "field.hpp"
 #include "host_field.hpp"
-#include "ntt64.hpp"
-
 #include "ntt_plan.hpp"
-
-namespace rg {
-// must match ntt_kernels.hpp (RadixOf + 8, kMinTiledP)
-static int pmax_of(int L) { return (L <= 2 ? 4 : 3) + 8; }
-static const int kMinTiledP = 6;
-}  // namespace rg
 
 struct rg_ntt {
   rg_field f;
   int N, logN, negacyclic;
-  bool shoup, tiled;
-  bool halving = true;  // wide fields: rank_inv == N^-1 (finalize)
   std::vector<uint64_t> h_tw, h_twinv, h_ninv;  // Montgomery reps, [N][L]
-  rg::DevBuf d_tw, d_twinv;                     // kernel format
-  rg::DevBuf d_tw_mont, d_twinv_mont;           // L = 1, 2^16, ntt64_mont_ok: single Montgomery words (ntt64.hpp MONT)
-  std::vector<rg::PassDesc> passes;             // forward order
-  uint64_t nsc[16], nsc_sh, w1n[16], w1n_sh;
-  uint64_t nsc_mont = 0, w1n_mont = 0;  // N^-1 and twInv[1] N^-1 in Montgomery form (with d_tw_mont)
-  std::unique_ptr<rg::Aux> aux;  // L = 4: helper stream of ntt256_run's split (ntt_l4_fast.hip)
+  rg::DevBuf d_tw, d_twinv;                     // the format the plan's routes read (finalize)
+  uint64_t nsc[16], nsc_sh, w1n[16], w1n_sh;    // rank_inv and twInv[1] rank_inv in that format
+  rg::NttLaunch dir[2];          // forward, inverse: all of a launch but in, out and batch
+  std::unique_ptr<rg::Aux> aux;  // Fast256: helper stream of ntt256_run's split (ntt_l4_fast.hip)
   int device = 0;                // the tables and the helper stream live on this device
 };
 
@@ -134,118 +125,144 @@ static rg_status build_tables(rg_ntt* t) {
   return RG_OK;
 }
 
+// Lazy64: append the lane-ordered ROW last-round copy for ntt16_pass (ntt64.hpp), W words per entry
+static void add_row_copy(std::vector<uint64_t>& v, size_t W) {
+  const size_t base = v.size();
+  v.resize(base + W * 256 * 192);
+  for (int r = 0; r < 256; ++r)
+    for (int tt = 0; tt < 32; ++tt) {
+      for (int g = 0; g < 2; ++g) {
+        const size_t src = (size_t)(1 << 14) + 64 * r + 2 * tt + g, dst = (size_t)r * 192 + 32 * g + tt;
+        for (size_t c = 0; c < W; ++c) v[base + W * dst + c] = v[W * src + c];
+      }
+      for (int j = 0; j < 4; ++j) {
+        const size_t src = (size_t)(1 << 15) + 128 * r + 4 * tt + j, dst = (size_t)r * 192 + 64 + 32 * j + tt;
+        for (size_t c = 0; c < W; ++c) v[base + W * dst + c] = v[W * src + c];
+      }
+    }
+}
+
+// The four table formats, each for both directions.  finalize() has left rank_inv and
+// twInv[1] rank_inv in t->nsc / t->w1n as Montgomery reps, the form of every format but Shoup's.
+
+// L = 1, q < 2^63: the plain twiddle (Montgomery rep * R^-1) and its Shoup quotient,
+// shoup(v, w) == v * w mod q == mont(v, w*R); the two constants likewise
+static rg_status upload_shoup(rg_ntt* t, bool row_copy) {
+  const int N = t->N;
+  const uint64_t q = t->f.q[0];
+  HostField H(&t->f);
+  std::vector<uint64_t> a((size_t)2 * N), b((size_t)2 * N);
+  for (int i = 0; i < N; ++i) {
+    uint64_t w, wi;
+    H.from_mont(&w, &t->h_tw[i]);
+    H.from_mont(&wi, &t->h_twinv[i]);
+    a[2 * i] = w;
+    a[2 * i + 1] = h_shoup(w, q);
+    b[2 * i] = wi;
+    b[2 * i + 1] = h_shoup(wi, q);
+  }
+  if (row_copy) {
+    add_row_copy(a, 2);
+    add_row_copy(b, 2);
+  }
+  RG_TRY(t->d_tw.upload(a.data(), a.size() * 8));
+  RG_TRY(t->d_twinv.upload(b.data(), b.size() * 8));
+  const uint64_t w1n = t->w1n[0];
+  H.from_mont(&t->nsc[0], &t->h_ninv[0]);
+  H.from_mont(&t->w1n[0], &w1n);
+  t->nsc_sh = h_shoup(t->nsc[0], q);
+  t->w1n_sh = h_shoup(t->w1n[0], q);
+  return RG_OK;
+}
+
+// Lazy64 with the Montgomery product (ntt64.hpp MONT): one word per twiddle, then the ROW copy
+static rg_status upload_mont64(rg_ntt* t) {
+  std::vector<uint64_t> a(t->h_tw), b(t->h_twinv);
+  add_row_copy(a, 1);
+  add_row_copy(b, 1);
+  RG_TRY(t->d_tw.upload(a.data(), a.size() * 8));
+  return t->d_twinv.upload(b.data(), b.size() * 8);
+}
+
+// wide fields whose inverse runs on ntt_wide_pass: the inverse table is twInv[i] / 2 (that kernel
+// halves every stage instead of scaling by N^-1 at the end)
+static rg_status upload_wide(rg_ntt* t) {
+  const int N = t->N, L = t->f.L;
+  RG_TRY(t->d_tw.upload(t->h_tw.data(), t->h_tw.size() * 8));
+  std::vector<uint64_t> b(t->h_twinv.size());
+  for (int i = 0; i < N; ++i) {
+    const uint64_t* x = &t->h_twinv[(size_t)i * L];
+    uint64_t* z = &b[(size_t)i * L];
+    uint64_t c = 0;
+    if (x[0] & 1) c = HostField::add_n(z, x, t->f.q, L);
+    else memcpy(z, x, 8 * L);
+    for (int l = 0; l < L; ++l) z[l] = (z[l] >> 1) | ((l + 1 < L ? z[l + 1] : c) << 63);
+  }
+  return t->d_twinv.upload(b.data(), b.size() * 8);
+}
+
+static rg_status upload_plain(rg_ntt* t) {
+  RG_TRY(t->d_tw.upload(t->h_tw.data(), t->h_tw.size() * 8));
+  return t->d_twinv.upload(t->h_twinv.data(), t->h_twinv.size() * 8);
+}
+
+// the helper stream of ntt256_run's two-half split (ntt_l4_fast.hip)
+static rg_status create_helper_stream(rg_ntt* t) {
+  t->aux.reset(new Aux());
+  RG_HIP(hipStreamCreateWithFlags(&t->aux->s, hipStreamNonBlocking));
+  RG_HIP(hipEventCreateWithFlags(&t->aux->fork, hipEventDisableTiming));
+  RG_HIP(hipEventCreateWithFlags(&t->aux->join, hipEventDisableTiming));
+  return RG_OK;
+}
+
+// Polynomials per pass pair.  Tiled in two passes: chunks of 192 MiB, so the pass-to-pass
+// intermediate stays in the 256 MiB Infinity Cache; Lazy64: the whole batch.  The NttChunkMb
+// switch (experiments build) sets the size for both; nothing else chunks.
+static size_t chunk_polys(const NttRouting& r, size_t poly_bytes) {
+  const bool tiled2 = r.route == NttRoute::Tiled && r.npasses == 2;
+  const char* e = knob(Knob::NttChunkMb);
+  if (!(tiled2 || (e && r.route == NttRoute::Lazy64))) return ~(size_t)0 >> 1;
+  return std::max<size_t>(1, ((size_t)(e ? atoi(e) : 192) << 20) / poly_bytes);
+}
+
+// Everything a plan decides, once: the route per direction (ntt_route.hpp), then only the tables
+// and the helper stream those routes use, then the two launch descriptions run() starts from.
 static rg_status finalize(rg_ntt* t) {
   const int N = t->N, L = t->f.L;
   RG_HIP(hipGetDevice(&t->device));
   HostField H(&t->f);
-  // pass plan: tiled passes of P in [kMinTiledP, pmax] for L <= 4; per-stage otherwise
-  const int pm = pmax_of(L);
-  t->passes.clear();
-  t->tiled = (L <= 4) && t->logN >= kMinTiledP && t->logN <= 2 * pm;
-  if (t->tiled) {
-    if (t->logN <= pm) {
-      t->passes.push_back({0, t->logN});
-    } else {
-      int pa = t->logN / 2;
-      if (pa < kMinTiledP) pa = kMinTiledP;
-      t->passes.push_back({0, pa});
-      t->passes.push_back({pa, t->logN - pa});
-    }
-  }
-  uint64_t w1n[16];
+  // log N halvings give exactly N^-1: a table-built plan whose rank_inv is anything else keeps
+  // the per-stage inverse, which multiplies by the caller's rank_inv (ntt.go:242-243)
+  uint64_t n[16], ninv[16];
+  H.from_u64(n, (uint64_t)N);
+  H.inverse(ninv, n);
+  const bool halving = H.eq(ninv, &t->h_ninv[0]);
+  const char* sw = knob(Knob::NttKernel);
+  const NttRouting r[2] = {ntt_route(L, t->f.q, t->logN, false, halving, sw),
+                           ntt_route(L, t->f.q, t->logN, true, halving, sw)};
   const uint64_t* twi1 = N >= 2 ? &t->h_twinv[(size_t)1 * L] : H.one;
-  H.mul(w1n, twi1, &t->h_ninv[0]);  // twInv[1] * N^-1 for the fused last inverse stage
-  t->shoup = (L == 1) && (t->f.q[0] >> 63) == 0;
-  if (t->shoup) {
-    // tables hold the plain twiddle (Montgomery rep * R^-1) and its Shoup quotient:
-    // shoup(v, w) == v * w mod q == mont(v, w*R).
-    const uint64_t q = t->f.q[0];
-    std::vector<uint64_t> a((size_t)2 * N), b((size_t)2 * N);
-    for (int i = 0; i < N; ++i) {
-      uint64_t w, wi;
-      H.from_mont(&w, &t->h_tw[i]);
-      H.from_mont(&wi, &t->h_twinv[i]);
-      a[2 * i] = w;
-      a[2 * i + 1] = h_shoup(w, q);
-      b[2 * i] = wi;
-      b[2 * i + 1] = h_shoup(wi, q);
-    }
-    if (t->logN == 16) {  // lane-ordered ROW last-round copy for ntt16_pass (ntt64.hpp), W words per entry
-      auto add_row_copy = [&](std::vector<uint64_t>& v, size_t W) {
-        const size_t base = v.size();
-        v.resize(base + W * 256 * 192);
-        for (int r = 0; r < 256; ++r)
-          for (int tt = 0; tt < 32; ++tt) {
-            for (int g = 0; g < 2; ++g) {
-              const size_t src = (size_t)(1 << 14) + 64 * r + 2 * tt + g, dst = (size_t)r * 192 + 32 * g + tt;
-              for (size_t c = 0; c < W; ++c) v[base + W * dst + c] = v[W * src + c];
-            }
-            for (int j = 0; j < 4; ++j) {
-              const size_t src = (size_t)(1 << 15) + 128 * r + 4 * tt + j, dst = (size_t)r * 192 + 64 + 32 * j + tt;
-              for (size_t c = 0; c < W; ++c) v[base + W * dst + c] = v[W * src + c];
-            }
-          }
-      };
-      add_row_copy(a, 2);
-      add_row_copy(b, 2);
-      // The Montgomery-product kernels read the reference's own representation, one word per
-      // twiddle.  The Shoup tables above stay: the generic kernels read them.
-      if (ntt64_mont_ok(q)) {
-        std::vector<uint64_t> am(t->h_tw.begin(), t->h_tw.begin() + N), bm(t->h_twinv.begin(), t->h_twinv.begin() + N);
-        add_row_copy(am, 1);
-        add_row_copy(bm, 1);
-        RG_TRY(t->d_tw_mont.upload(am.data(), am.size() * 8));
-        RG_TRY(t->d_twinv_mont.upload(bm.data(), bm.size() * 8));
-        t->nsc_mont = t->h_ninv[0];
-        t->w1n_mont = w1n[0];
-      }
-    }
-    RG_TRY(t->d_tw.upload(a.data(), a.size() * 8));
-    RG_TRY(t->d_twinv.upload(b.data(), b.size() * 8));
-    uint64_t nv, wv;
-    H.from_mont(&nv, &t->h_ninv[0]);
-    H.from_mont(&wv, w1n);
-    t->nsc[0] = nv;
-    t->nsc_sh = h_shoup(nv, q);
-    t->w1n[0] = wv;
-    t->w1n_sh = h_shoup(wv, q);
-  } else if (L == 7 || L == 14) {
-    // wide fields: the inverse table is followed by twInv[i] / 2 (ntt_wide.hpp's inverse halves
-    // every stage instead of scaling by N^-1 at the end); the per-stage kernels read the first half
-    RG_TRY(t->d_tw.upload(t->h_tw.data(), t->h_tw.size() * 8));
-    std::vector<uint64_t> b(2 * t->h_twinv.size());
-    const size_t half = t->h_twinv.size();
-    memcpy(b.data(), t->h_twinv.data(), half * 8);
-    for (int i = 0; i < N; ++i) {
-      const uint64_t* x = &t->h_twinv[(size_t)i * L];
-      uint64_t* z = &b[half + (size_t)i * L];
-      uint64_t c = 0;
-      if (x[0] & 1) c = HostField::add_n(z, x, t->f.q, L);
-      else memcpy(z, x, 8 * L);
-      for (int l = 0; l < L; ++l) z[l] = (z[l] >> 1) | ((l + 1 < L ? z[l + 1] : c) << 63);
-    }
-    RG_TRY(t->d_twinv.upload(b.data(), b.size() * 8));
-    memcpy(t->nsc, &t->h_ninv[0], 8 * L);
-    memcpy(t->w1n, w1n, 8 * L);
-    t->nsc_sh = t->w1n_sh = 0;
-    // log N halvings give exactly N^-1: a table-built plan whose rank_inv is anything else keeps
-    // the per-stage inverse, which multiplies by the caller's rank_inv (ntt.go:242-243)
-    uint64_t n[16], ninv[16];
-    H.from_u64(n, (uint64_t)N);
-    H.inverse(ninv, n);
-    t->halving = H.eq(ninv, &t->h_ninv[0]);
-  } else {
-    RG_TRY(t->d_tw.upload(t->h_tw.data(), t->h_tw.size() * 8));
-    RG_TRY(t->d_twinv.upload(t->h_twinv.data(), t->h_twinv.size() * 8));
-    memcpy(t->nsc, &t->h_ninv[0], 8 * L);
-    memcpy(t->w1n, w1n, 8 * L);
-    t->nsc_sh = t->w1n_sh = 0;
-  }
-  if (L == 4 && (t->logN == 15 || t->logN == 16)) {
-    t->aux.reset(new Aux());
-    RG_HIP(hipStreamCreateWithFlags(&t->aux->s, hipStreamNonBlocking));
-    RG_HIP(hipEventCreateWithFlags(&t->aux->fork, hipEventDisableTiming));
-    RG_HIP(hipEventCreateWithFlags(&t->aux->join, hipEventDisableTiming));
+  memcpy(t->nsc, &t->h_ninv[0], 8 * L);
+  H.mul(t->w1n, twi1, &t->h_ninv[0]);  // twInv[1] * N^-1 for the fused last inverse stage
+  t->nsc_sh = t->w1n_sh = 0;
+  if (r[0].mont) RG_TRY(upload_mont64(t));
+  else if (r[0].shoup) RG_TRY(upload_shoup(t, r[0].route == NttRoute::Lazy64));
+  else if (r[1].route == NttRoute::Wide) RG_TRY(upload_wide(t));
+  else RG_TRY(upload_plain(t));
+  if (r[0].route == NttRoute::Fast256) RG_TRY(create_helper_stream(t));
+  for (int d = 0; d < 2; ++d) {
+    NttLaunch& p = t->dir[d];  // in, out, batch: run()
+    static_cast<NttRouting&>(p) = r[d];
+    p.inv = d == 1;
+    p.tw = (d ? t->d_twinv : t->d_tw).as<uint64_t>();
+    p.q = t->f.q;
+    p.qinv = t->f.qinv;
+    p.nsc = t->nsc;
+    p.nsc_sh = t->nsc_sh;
+    p.w1n = t->w1n;
+    p.w1n_sh = t->w1n_sh;
+    p.logN = t->logN;
+    p.chunk_polys = chunk_polys(r[d], (size_t)N * L * 8);
+    p.aux = t->aux.get();
   }
   return RG_OK;
 }
@@ -258,40 +275,19 @@ static rg_status run(const rg_ntt* t, uint64_t* out, const uint64_t* in, size_t 
     set_last_error("rg_ntt plan used on device " + std::to_string(cur) + ", created on " + std::to_string(t->device));
     return RG_ERR_INVALID;
   }
-  NttLaunch p;
+  NttLaunch p = t->dir[inv];
   p.in = in;
   p.out = out;
-  p.tw = inv ? t->d_twinv.as<uint64_t>() : t->d_tw.as<uint64_t>();
-  p.q = t->f.q;
-  p.qinv = t->f.qinv;
-  p.nsc = t->nsc;
-  p.nsc_sh = t->nsc_sh;
-  p.w1n = t->w1n;
-  p.w1n_sh = t->w1n_sh;
-  p.tw_mont = inv ? t->d_twinv_mont.as<uint64_t>() : t->d_tw_mont.as<uint64_t>();
-  p.nsc_mont = t->nsc_mont;
-  p.w1n_mont = t->w1n_mont;
-  p.logN = t->logN;
-  p.shoup = t->shoup;
-  p.inv = inv;
-  p.tiled = t->tiled;
-  p.halving = t->halving;
-  p.passes = t->passes.data();
-  p.npasses = (int)t->passes.size();
   p.batch = batch;
-  p.aux = t->aux.get();
+  switch (p.route) {
+    case NttRoute::Lazy64: return ntt64_run(p, st);
+    case NttRoute::Fast256: return ntt256_run(p, st);
+    default: break;  // Tiled, Stages, Wide: the limb count's own unit
+  }
   switch (t->f.L) {
-    case 1: {
-      bool done = false;
-      RG_TRY(ntt64_run(p, st, &done));
-      return done ? RG_OK : ntt_run_L1(p, st);
-    }
+    case 1: return ntt_run_L1(p, st);
     case 2: return ntt_run_L2(p, st);
-    case 4: {
-      bool done = false;
-      RG_TRY(ntt256_run(p, st, &done));
-      return done ? RG_OK : ntt_run_L4(p, st);
-    }
+    case 4: return ntt_run_L4(p, st);
     case 7: return ntt_run_L7(p, st);
     case 14: return ntt_run_L14(p, st);
     default: return RG_ERR_UNSUPPORTED;
@@ -394,11 +390,9 @@ static rg_status host_call(const rg_ntt* t, uint64_t* out, const uint64_t* in, s
   if (batch == 0) return RG_OK;
   const size_t bytes = batch * (size_t)t->N * t->f.L * 8;
   DevBuf buf;
-  RG_TRY(buf.alloc(bytes));
-  RG_HIP(hipMemcpy(buf.p, in, bytes, hipMemcpyHostToDevice));
+  RG_TRY(buf.upload(in, bytes));
   RG_TRY(dev_call(t, buf.as<uint64_t>(), buf.as<uint64_t>(), batch, nullptr, inv));
-  RG_HIP(hipMemcpy(out, buf.p, bytes, hipMemcpyDeviceToHost));
-  return RG_OK;
+  return buf.download(out, bytes);
 }
 
 rg_status rg_ntt_fwd(const rg_ntt* t, uint64_t* out, const uint64_t* in, size_t batch) {

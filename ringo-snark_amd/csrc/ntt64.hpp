@@ -2,8 +2,8 @@
 //
 // The bound is q < 2^63 (2q fits a word), not 2^64/3: the sum of two lazy values, < 4q < 2^65, is
 // compared against 2q through its carry bit (lazy_add's c, fwd_bfly_x / inv_bfly_x's c2), so 3q
-// may pass 2^64.  ntt_l1_lazy.hip gates on exactly this; tests/test_gpu_ntt_synthetic.py runs
-// q = 0x7ffffff900000001 (3q > 2^64) through every pass.
+// may pass 2^64.  ntt_route.hpp's Lazy64 route gates on exactly this;
+// tests/test_gpu_ntt_synthetic.py runs q = 0x7ffffff900000001 (3q > 2^64) through every pass.
 // Values between butterfly stages live in [0, 2q) ("Harvey" lazy form); only the last stage of
 // a transform maps them to the canonical residues the reference produces (gnark fully reduces,
 // jindo/internal/zp/element.go:397-466), so every output limb is bit-identical to ntt.go.
@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "field.hpp"
+#include "ntt_route.hpp"
 
 namespace rg {
 
@@ -58,10 +59,9 @@ RG_HD Q64 make_q64(uint64_t q) {
 // No 64-bit intermediate overflows, and the forward butterfly's x + t (x < 2q) fits 64 bits,
 // when 3q + ceil(2 q^2 / 2^64) + 2^33 < 2^64: p2 = y0 w1 + y1 w0 + hi(p0) + 2^32 < 3q + 2^33,
 // p3 < y1 w1 + 2^32 + q < 2q^2/2^64 + q + 2^33, x + t < 3q + ceil(2 q^2 / 2^64).  That is
-// q1 <= 0x47e0f66a (q / 2^64 <= 0.28078), ntt64_mont_ok below; tests/test_mont64_host.py checks
-// the constant against the inequality and the product against integers at both ends.
-constexpr uint32_t kMontMaxQ1 = 0x47e0f66au;
-RG_HD bool ntt64_mont_ok(uint64_t q) { return (uint32_t)q == 1u && (q >> 32) != 0 && (q >> 32) <= kMontMaxQ1; }
+// q1 <= 0x47e0f66a (q / 2^64 <= 0.28078): kMontMaxQ1 and ntt64_mont_ok of ntt_route.hpp, where the
+// plan's route is decided; tests/test_mont64_host.py checks the constant against the inequality and
+// the product against integers at both ends.
 
 // portable form (host tables, tests); the device kernels use mont_x below
 RG_HD uint64_t mont64(uint64_t y, uint64_t w, uint32_t q1) {

@@ -25,7 +25,6 @@
 //   sees ~one read and one write per element per transform.
 #pragma once
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -51,16 +50,6 @@ struct NttArgs {
   int qlo1;             // q mod 2^32 == 1 (L == 1 fast reduction)
   long long total_sub;  // batch * N / 2^P
 };
-
-// per-L register radix (points per thread = 2^R) keeps VGPR use near 128
-template <int L>
-struct RadixOf {
-  static constexpr int value = (L == 1 || L == 2) ? 4 : (L <= 4 ? 3 : (L <= 7 ? 2 : 2));
-};
-template <int L>
-constexpr int pmax_of() {
-  return RadixOf<L>::value + 8;
-}
 
 template <int L, bool SHOUP>
 struct Tw {
@@ -484,9 +473,6 @@ __global__ __launch_bounds__(256) void ntt_stage_kernel(NttArgs<L> a, int lt, in
   }
 }
 
-// smallest P handled by the LDS-tiled pass kernel (smaller transforms use stage kernels)
-constexpr int kMinTiledP = 6;
-
 template <int L>
 static void fill_args(NttArgs<L>& a, const NttLaunch& p) {
   memcpy(a.F.q, p.q, 8 * L);
@@ -528,8 +514,6 @@ static rg_status dispatch_P(int p, const NttArgs<L>& a, hipStream_t st) {
   }
 }
 
-}  // namespace rg
-
 // ----------------------------------------------------------------------------------------
 // 2-round pass specialisation (P = 8 = 2 x radix-16), the shape of every pass of the
 // degree-2^16 transform.  Compared with ntt_pass_kernel:
@@ -546,8 +530,6 @@ static rg_status dispatch_P(int p, const NttArgs<L>& a, hipStream_t st) {
 // LDS layout lds[l][s * PADN + pad(x)]: COL uses pad(x) = x, PADN = 257; ROW uses
 // pad(x) = x + x/16, PADN = 272 (see DESIGN.md for the bank analysis).
 // ----------------------------------------------------------------------------------------
-namespace rg {
-
 template <bool COL>
 struct R2Layout {
   static constexpr int PADN = COL ? 257 : 272;
@@ -822,12 +804,6 @@ static rg_status dispatch_r2(bool col, const NttArgs<L>& a, hipStream_t st) {
   return col ? launch_r2<L, INV, SHOUP, SCALE, true>(a, st) : launch_r2<L, INV, SHOUP, SCALE, false>(a, st);
 }
 
-}  // namespace rg
-
-namespace rg {
-
-}  // namespace rg
-
 // ----------------------------------------------------------------------------------------
 // Radix-8 pass for single-word Shoup fields (P = 8 as rounds of 3 + 3 + 2 bits).
 // 8 points per thread (16 VGPRs of data instead of 32) and 512-thread workgroups holding 16
@@ -837,8 +813,6 @@ namespace rg {
 // one.  Lane mapping as in ntt_r2_kernel: COL s fastest (16 columns -> 128 B runs),
 // ROW t fastest (32 consecutive points).  LDS images per exchange: see ntt_r8_kernel.
 // ----------------------------------------------------------------------------------------
-namespace rg {
-
 template <int RK, bool INV, bool SCALE, bool QLO1>
 __device__ __forceinline__ void r8_round(const NttArgs<1>& a, uint64_t (&e)[8], int LO, long long hi, int t,
                                          bool uniform) {
@@ -1038,23 +1012,12 @@ static rg_status launch_r8(const NttArgs<1>& a, hipStream_t st) {
   return a.qlo1 ? launch_r8_q<INV, SCALE, COL, true>(a, st) : launch_r8_q<INV, SCALE, COL, false>(a, st);
 }
 
-
-}  // namespace rg
-
-namespace rg {
-
 template <int L, bool SHOUP>
 static rg_status run_tiled(const NttLaunch& p, hipStream_t st) {
   const size_t N = (size_t)1 << p.logN;
   const size_t poly_u64 = N * L;
-  // chunk the batch so the pass-to-pass intermediate stays in the 256 MiB Infinity Cache
-  static size_t chunk_bytes = 0;
-  if (!chunk_bytes) {  // RINGO_NTT_CHUNK_MB overrides the Infinity-Cache-sized chunk (tuning)
-    const char* e = knob(Knob::NttChunkMb);
-    chunk_bytes = (size_t)(e ? atoi(e) : 192) << 20;
-  }
-  size_t chunk = std::max<size_t>(1, chunk_bytes / (poly_u64 * 8));
-  if (p.npasses == 1) chunk = p.batch;
+  // the batch in chunks, so the pass-to-pass intermediate stays in the 256 MiB Infinity Cache
+  const size_t chunk = p.chunk_polys;
   NttArgs<L> a;
   fill_args<L>(a, p);
   for (size_t b0 = 0; b0 < p.batch; b0 += chunk) {

@@ -2,6 +2,6 @@
 #include "ntt_kernels.hpp"
 namespace rg {
 rg_status ntt_run_L4(const NttLaunch& p, hipStream_t st) {
-  return p.tiled ? run_tiled<4, false>(p, st) : run_stages<4, false>(p, st);
+  return p.route == NttRoute::Tiled ? run_tiled<4, false>(p, st) : run_stages<4, false>(p, st);
 }
 }  // namespace rg

@@ -1,7 +1,7 @@
-// ntt_l4_fast.hip -- dispatch of the 4-limb degree-2^16 / 2^15 kernels (ntt256.hpp) for q = 1 mod 2^64,
-// q < 2^255 (the Jindo default prime q255).  Other 4-limb shapes keep the generic CIOS kernels
-// of ntt_kernels.hpp.  RINGO_NTT_KERNEL=r... forces the generic path (A/B switch; experiments
-// build only, common.hpp).
+// ntt_l4_fast.hip -- the Fast256 route's runner: the 4-limb degree-2^16 / 2^15 kernels (ntt256.hpp)
+// for q = 1 mod 2^64, q < 2^255 (the Jindo default prime q255).  ntt_route.hpp decides which plans
+// come here, and only those own a helper stream; this unit derives Ntt256Args from the modulus and
+// splits the batch over the two streams.
 #include "ntt256.hpp"
 #include "ntt_plan.hpp"
 
@@ -69,14 +69,7 @@ static rg_status run_split(Ntt256Args a, const NttLaunch& p, hipStream_t st) {
 }
 
 // N = 2^16 (passes 8 + 8) and N = 2^15 (7 + 8: the Buckler witness rank of the bench)
-rg_status ntt256_run(const NttLaunch& p, hipStream_t st, bool* handled) {
-  *handled = false;
-  if (p.npasses != 2 || p.passes[1].P != 8 || !((p.logN == 16 && p.passes[0].P == 8) || (p.logN == 15 && p.passes[0].P == 7)))
-    return RG_OK;
-  if (p.q[0] != 1 || (p.q[3] >> 63) != 0) return RG_OK;
-  const char* e = knob(Knob::NttKernel);
-  if (e && e[0] == 'r') return RG_OK;
-  *handled = true;
+rg_status ntt256_run(const NttLaunch& p, hipStream_t st) {
   const size_t N = (size_t)1 << p.logN;
   Ntt256Args a{};
   a.tw = p.tw;

@@ -1,6 +1,7 @@
-// ntt_lwide.hip -- wide buckler fields (zp440: 7 limbs, zp880: 14 limbs): the LDS-tiled pass
-// kernel of ntt_wide.hpp for N <= 2^16 (two passes: COL then ROW; one pass for N <= 2^8), the
-// per-stage kernels of ntt_kernels.hpp for larger ranks or a modulus without a spare top bit.
+// ntt_lwide.hip -- wide buckler fields (zp440: 7 limbs, zp880: 14 limbs): the Wide route's runner
+// (the LDS-tiled pass kernel of ntt_wide.hpp over the plan's passes: COL then ROW, one pass for
+// N <= 2^8) and the Stages route's per-stage kernels of ntt_kernels.hpp.  ntt_route.hpp decides
+// per direction which of the two a plan takes; this unit derives WideArgs from the modulus.
 #include "ntt_kernels.hpp"
 #include "ntt_wide.hpp"
 
@@ -8,14 +9,11 @@ namespace rg {
 
 template <int L>
 static rg_status wide_run(const NttLaunch& p, hipStream_t st) {
+  if (p.route != NttRoute::Wide) return run_stages<L, false>(p, st);
   const int logN = p.logN;
-  const bool spare = (p.q[L - 1] >> 63) == 0;
-  const char* k = knob(Knob::NttKernel);  // experiments build: RINGO_NTT_KERNEL=stage (A/B)
-  if (logN < 1 || logN > 16 || !spare || (p.inv && !p.halving) || (k && k[0] == 's')) return run_stages<L, false>(p, st);
   WideArgs a;
   memset(&a, 0, sizeof(a));
-  // inverse: the halved copy of twInv that ntt.hip's finalize() appends to the table
-  a.tw = p.inv ? p.tw + ((size_t)1 << logN) * L : p.tw;
+  a.tw = p.tw;  // inverse: twInv[i] / 2 (ntt.hip upload_wide)
   for (int l = 0; l < L; ++l) {
     a.q[2 * l] = (uint32_t)p.q[l];
     a.q[2 * l + 1] = (uint32_t)(p.q[l] >> 32);
@@ -28,24 +26,11 @@ static rg_status wide_run(const NttLaunch& p, hipStream_t st) {
     a.q28[k] = (uint32_t)v & 0x0FFFFFFFu;
   }
   a.logN = logN;
-  // passes in forward order: (G0, P)
-  int G0s[2], Ps[2], np;
-  if (logN <= 8) {
-    np = 1;
-    G0s[0] = 0;
-    Ps[0] = logN;
-  } else {
-    np = 2;
-    G0s[0] = 0;
-    Ps[0] = logN / 2;
-    G0s[1] = logN / 2;
-    Ps[1] = logN - logN / 2;
-  }
   const int base_cpt = 1;  // one 256-point sub-transform per workgroup at P = 8: 14 / 28 KiB of LDS, so LDS does not cap occupancy below the VGPRs
-  for (int k = 0; k < np; ++k) {
-    const int i = p.inv ? np - 1 - k : k;
-    a.G0 = G0s[i];
-    a.P = Ps[i];
+  for (int k = 0; k < p.npasses; ++k) {
+    const PassDesc& ps = p.inv ? p.passes[p.npasses - 1 - k] : p.passes[k];
+    a.G0 = ps.G0;
+    a.P = ps.P;
     a.logS = logN - a.G0 - a.P;
     a.cpt = std::max(base_cpt, 256 >> a.P);
     if (a.logS > 0) a.cpt = std::min(a.cpt, 1 << a.logS);  // a COL tile stays inside one row of columns

@@ -1,42 +1,35 @@
-// ntt_plan.hpp -- what ntt.hip hands to the per-limb-count kernel translation units.
+// ntt_plan.hpp -- what ntt.hip hands to the runners of the per-limb-count kernel translation units:
+// one NttLaunch per direction, filled when the plan is created (route, passes, tables, constants,
+// chunk size; ntt.hip finalize()), and the runners that ntt.hip's run() picks among by route.
 #pragma once
 #include <mutex>
 
 #include "common.hpp"
+#include "ntt_route.hpp"
 
 namespace rg {
 
-struct PassDesc {
-  int G0, P;
-};
-
-// Everything a per-L translation unit needs from the host plan.
-struct NttLaunch {
+struct NttLaunch : NttRouting {  // the direction's route, table format and passes (ntt_route.hpp)
+  // set by every call
   const uint64_t* in;
   uint64_t* out;
-  const uint64_t* tw;
+  size_t batch;
+  // fixed for the plan and the direction
+  bool inv;
+  const uint64_t* tw;  // the direction's table in the route's format
   const uint64_t* q;
   uint64_t qinv;
-  const uint64_t* nsc;
+  const uint64_t* nsc;  // N^-1 (rank_inv) and twInv[1] N^-1 in the table's form; *_sh their Shoup quotients
   uint64_t nsc_sh;
   const uint64_t* w1n;
   uint64_t w1n_sh;
-  // L = 1, N = 2^16, ntt64_mont_ok(q) (ntt64.hpp): the direction's table as single words in
-  // Montgomery form with its lane-ordered ROW copy, N^-1 and twInv[1] N^-1 likewise; else null
-  const uint64_t* tw_mont = nullptr;
-  uint64_t nsc_mont = 0, w1n_mont = 0;
   int logN;
-  bool shoup, inv, tiled;
-  bool halving;  // rank_inv == N^-1: the wide pass's per-stage halving scales the inverse correctly
-  const PassDesc* passes;  // forward order
-  int npasses;
-  size_t batch;
-  // the plan's helper stream for ntt256_run's two-half split (null: single stream); the mutex
-  // serialises the fork/join enqueue of concurrent callers, which share the events
-  struct Aux* aux = nullptr;
+  size_t chunk_polys;  // Tiled (two passes), Lazy64: polynomials per pass pair
+  struct Aux* aux;  // Fast256: the plan's helper stream for the two-half split; else null
 };
 
-// a helper stream and the two events that fork it from and join it back to the caller's stream
+// a helper stream and the two events that fork it from and join it back to the caller's stream;
+// the mutex serialises the fork/join enqueue of concurrent callers, which share the events
 struct Aux {
   hipStream_t s = nullptr;
   hipEvent_t fork = nullptr, join = nullptr;
@@ -52,14 +45,14 @@ struct Aux {
 const rg_field* ntt_field(const rg_ntt* t);
 bool ntt_negacyclic(const rg_ntt* t);
 
+// Tiled or Stages (L7, L14: Wide or Stages) by p.route, one unit per limb count
 rg_status ntt_run_L1(const NttLaunch& p, hipStream_t st);
-// lazy single-word pass kernels (ntt_l1_lazy.hip); sets *handled when the shape is covered
-rg_status ntt64_run(const NttLaunch& p, hipStream_t st, bool* handled);
-// 4-limb degree-2^16 kernels for q = 1 mod 2^64 (ntt_l4_fast.hip)
-rg_status ntt256_run(const NttLaunch& p, hipStream_t st, bool* handled);
 rg_status ntt_run_L2(const NttLaunch& p, hipStream_t st);
 rg_status ntt_run_L4(const NttLaunch& p, hipStream_t st);
 rg_status ntt_run_L7(const NttLaunch& p, hipStream_t st);
 rg_status ntt_run_L14(const NttLaunch& p, hipStream_t st);
+// Lazy64 (ntt_l1_lazy.hip) and Fast256 (ntt_l4_fast.hip)
+rg_status ntt64_run(const NttLaunch& p, hipStream_t st);
+rg_status ntt256_run(const NttLaunch& p, hipStream_t st);
 
 }  // namespace rg

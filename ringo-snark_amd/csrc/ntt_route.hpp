@@ -1,0 +1,87 @@
+// ntt_route.hpp -- which of the five NTT kernel families serves a plan, and in which passes:
+// decided once, when the plan is created (ntt.hip finalize()), by ntt_route() below.  HIP-free,
+// <stdint.h> only: tests/test_ntt_route_host.py compiles it with g++ and walks every field, rank,
+// direction and switch value.  DESIGN.md section 4.0 has the rules as a table.
+#pragma once
+#include <stdint.h>
+
+namespace rg {
+
+// per-L register radix (points per thread = 2^R) keeps VGPR use near 128
+constexpr int ntt_radix(int L) { return L <= 2 ? 4 : (L <= 4 ? 3 : 2); }
+constexpr int ntt_pmax(int L) { return ntt_radix(L) + 8; }  // most stages in one LDS-tiled pass
+template <int L>
+struct RadixOf {
+  static constexpr int value = ntt_radix(L);
+};
+template <int L>
+constexpr int pmax_of() {
+  return ntt_pmax(L);
+}
+// smallest P handled by the LDS-tiled pass kernel (smaller transforms use stage kernels)
+constexpr int kMinTiledP = 6;
+
+// The Montgomery twiddle product of the lazy passes (ntt64.hpp, MONT) needs
+// 3q + ceil(2 q^2 / 2^64) + 2^33 < 2^64, that is q1 = q >> 32 <= 0x47e0f66a (q / 2^64 <= 0.28078);
+// the derivation is at mont64 in ntt64.hpp, tests/test_mont64_host.py checks the constant.
+constexpr uint32_t kMontMaxQ1 = 0x47e0f66au;
+constexpr bool ntt64_mont_ok(uint64_t q) { return (uint32_t)q == 1u && (q >> 32) != 0 && (q >> 32) <= kMontMaxQ1; }
+
+enum class NttRoute : int {
+  Stages,   // ntt_stage_kernel, one launch per stage: whatever the others leave
+  Tiled,    // ntt_pass_kernel / ntt_r2 / ntt_r8, LDS-tiled: L <= 4, kMinTiledP <= logN <= 2 pmax
+  Lazy64,   // ntt16_pass (ntt64.hpp): L = 1, q < 2^63, q mod 2^32 == 1, logN = 16
+  Fast256,  // ntt256_pass (ntt256.hpp): L = 4, q[0] == 1, q < 2^255, logN = 15, 16
+  Wide      // ntt_wide_pass (ntt_wide.hpp): L = 7, 14, spare top bit, 1 <= logN <= 16
+};
+
+// a pass covers the P global stages [G0, G0 + P)
+struct PassDesc {
+  int G0, P;
+};
+
+struct NttRouting {
+  NttRoute route;
+  bool shoup;  // L = 1, q < 2^63: (w, w') Shoup pair tables and products (all routes but Lazy64 with mont)
+  bool mont;   // Lazy64 only: ntt64_mont_ok(q), single-word Montgomery tables and the MONT kernels
+  int npasses;
+  PassDesc passes[2];  // forward order; none for Stages
+};
+
+// one pass of logN when pa == logN, else pa stages then the rest
+inline void ntt_set_passes(NttRouting& r, int logN, int pa) {
+  r.npasses = pa < logN ? 2 : 1;
+  r.passes[0] = {0, pa};
+  if (pa < logN) r.passes[1] = {pa, logN - pa};
+}
+
+// L limbs of modulus q, N = 2^logN, one direction; halving: rank_inv == N^-1 (the wide inverse
+// halves per stage and so cannot scale by anything else); sw: the NttKernel switch of the
+// experiments build (common.hpp) or null: r* leaves Lazy64 and Fast256 to Tiled, s* Wide to Stages.
+inline NttRouting ntt_route(int L, const uint64_t* q, int logN, bool inv, bool halving, const char* sw) {
+  NttRouting r = {NttRoute::Stages, false, false, 0, {{0, 0}, {0, 0}}};
+  const bool generic = sw && sw[0] == 'r', per_stage = sw && sw[0] == 's';
+  if (L == 7 || L == 14) {
+    if (logN >= 1 && logN <= 16 && (q[L - 1] >> 63) == 0 && !(inv && !halving) && !per_stage) {
+      r.route = NttRoute::Wide;
+      ntt_set_passes(r, logN, logN <= 8 ? logN : logN / 2);  // COL then ROW
+    }
+    return r;
+  }
+  r.shoup = L == 1 && (q[0] >> 63) == 0;
+  if (r.shoup && logN == 16 && (uint32_t)q[0] == 1u && !generic) {
+    r.route = NttRoute::Lazy64;
+    r.mont = ntt64_mont_ok(q[0]);
+  } else if (L == 4 && (logN == 15 || logN == 16) && q[0] == 1 && (q[3] >> 63) == 0 && !generic) {
+    r.route = NttRoute::Fast256;
+  } else if (logN >= kMinTiledP && logN <= 2 * ntt_pmax(L)) {
+    r.route = NttRoute::Tiled;
+  } else {
+    return r;
+  }
+  const int half = logN / 2 < kMinTiledP ? kMinTiledP : logN / 2;
+  ntt_set_passes(r, logN, logN <= ntt_pmax(L) ? logN : half);
+  return r;
+}
+
+}  // namespace rg

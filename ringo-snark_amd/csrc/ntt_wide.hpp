@@ -21,8 +21,8 @@
 // table) instead of multiplying by N^-1 after the last one: log N halvings are N^-1, a halving is
 // ~3 D operations, and the butterfly keeps ONE product site (a second one for the N^-1 factor
 // doubled the I-cache footprint and pushed the 14-limb kernel past 256 VGPRs).  Requires
-// q < 2^(64L - 1) (checked by the launcher), so a Montgomery product of canonical inputs is
-// < 2q < 2^(64L).
+// q < 2^(64L - 1) (the Wide route's condition, ntt_route.hpp), so a Montgomery product of
+// canonical inputs is < 2q < 2^(64L).
 #pragma once
 #include <stdint.h>
 

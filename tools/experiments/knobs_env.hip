@@ -1,7 +1,9 @@
 // knobs_env.hip -- the experiments build's knob table (libringo_exp.so only; see
-// ringo-snark_amd/csrc/common.hpp).  Knobs come from the RINGO_* environment, read once; the
-// probe is per calling thread, so a probe window opened by bench.py's compute-floor leg cannot
-// change launches issued from another thread.
+// ringo-snark_amd/csrc/common.hpp).  Knobs come from the RINGO_* environment, read once: the NTT
+// knobs (RINGO_NTT_KERNEL, RINGO_NTT_CHUNK_MB) when an NTT plan is created, so set them before
+// the plan exists; a plan keeps the kernels it was created with.  The probe is per calling thread
+// and read by every call, so a probe window opened by bench.py's compute-floor leg cannot change
+// launches issued from another thread.
 #include <cstdlib>
 
 #include "../../ringo-snark_amd/csrc/common.hpp"
