@@ -15,6 +15,7 @@
 #include "field.hpp"
 #include "host_field.hpp"
 #include "ntt_plan.hpp"
+#include "ntt_tile.hpp"
 
 struct rg_ntt {
   rg_field f;
@@ -175,11 +176,19 @@ static rg_status upload_shoup(rg_ntt* t, bool row_copy) {
   return RG_OK;
 }
 
-// Lazy64 with the Montgomery product (ntt64.hpp MONT): one word per twiddle, then the ROW copy
+// Lazy64 with the Montgomery product (ntt64.hpp MONT): one word per twiddle, then the ROW copy,
+// then (inverse table) the plan's rank_inv and rank_inv twInv[1 .. 16) for the fold of the last
+// inverse round (ntt_tile.hpp): the plan's own rank_inv, whatever a table-built plan was given
 static rg_status upload_mont64(rg_ntt* t) {
   std::vector<uint64_t> a(t->h_tw), b(t->h_twinv);
   add_row_copy(a, 1);
   add_row_copy(b, 1);
+  HostField H(&t->f);
+  uint64_t fold[kNttFoldLen];
+  ntt_fold_consts(t->h_twinv.data(), t->h_ninv[0], [&](uint64_t* z, const uint64_t* x, const uint64_t* y) { H.mul(z, x, y); },
+                  fold);
+  if (b.size() != kNttFoldBase) return RG_ERR_INVALID;  // the kernels' compile-time offset
+  b.insert(b.end(), fold, fold + kNttFoldLen);
   RG_TRY(t->d_tw.upload(a.data(), a.size() * 8));
   return t->d_twinv.upload(b.data(), b.size() * 8);
 }
@@ -262,6 +271,7 @@ static rg_status finalize(rg_ntt* t) {
     p.w1n_sh = t->w1n_sh;
     p.logN = t->logN;
     p.chunk_polys = chunk_polys(r[d], (size_t)N * L * 8);
+    p.tile16 = ntt64_tile16(r[d].mont, sw);
     p.aux = t->aux.get();
   }
   return RG_OK;

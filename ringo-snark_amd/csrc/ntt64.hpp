@@ -26,6 +26,7 @@
 
 #include "field.hpp"
 #include "ntt_route.hpp"
+#include "ntt_tile.hpp"
 
 namespace rg {
 
@@ -342,7 +343,8 @@ struct Ntt64Args {
   // row r, stage 14: [r*192 + 32 g + t] = tw[2^14 + 64 r + 2 t + g]       (g < 2,  t < 32)
   //        stage 15: [r*192 + 64 + 32 j + t] = tw[2^15 + 128 r + 4 t + j] (j < 4)
   // MONT kernels: the same two tables as single words in Montgomery form (w 2^64 mod q, the
-  // reference's own representation), 8 B per entry, same indices
+  // reference's own representation), 8 B per entry, same indices; behind the inverse one, at
+  // kNttFoldBase, rank_inv and rank_inv twInv[1 .. 16) (ntt_tile.hpp: the fold of the last round)
   const uint64_t* tw;
   uint64_t q, q2;
   uint32_t nqhi, q1;      // -(q >> 32) mod 2^32 (Shoup), q >> 32 (MONT)
@@ -436,15 +438,14 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
   // there measured no faster: their lgkmcnt waits also wait for the exchange's LDS traffic.)
   constexpr bool UNIFORM = (COL || RP) && PAT == 0;
   constexpr bool MTW = PAT == 1 && (COL || RP) && (PROBE & 1) == 0;
-  auto xof = [&](int rho) -> uint32_t {
-    if (PAT == 0) return t + 32u * rho;
-    if (PAT == 1) return ((t >> 2) << 5) | ((uint32_t)rho << 2) | (t & 3u);
-    return 8u * t + rho;
-  };
-  constexpr int NPK = 1 << RK;
+  auto xof = [&](int rho) -> uint32_t { return ntt8_xof(PAT, t, rho); };
+  // rank_inv folded into this round's y-branch twiddles (ntt_tile.hpp): the round that holds global
+  // stage 0 of a MONT inverse.  The scaled twiddles are scalar loads from behind the table, like the
+  // round's plain ones; register 0 keeps w1n and the explicit product, as kernel arguments.
+  constexpr bool FOLD = MONT && INV && SCALE && COL && PAT == 0 && (PROBE & 1) == 0;
 #pragma unroll
   for (int sp = 0; sp < RK; ++sp) {
-    const int bw = INV ? sp : (RK - 1 - sp);
+    const int bw = ntt_round_bw(INV, RK, sp);
     const int b = LO + bw;
     const int k = 7 - b;
     const int half = 1 << bw;
@@ -452,14 +453,15 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
     uint64_t w[4], wp[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int grp = j / (NPK / 2), jj = j % (NPK / 2);
-      const int rho0 = grp * NPK + ((jj >> bw) << (bw + 1)) + (jj & (half - 1));
-      if ((jj & (half - 1)) != 0) {  // same x >> (b+1) as the previous pair
+      const int rho0 = ntt_pair_rho0(RK, bw, j);
+      const bool scaled = FOLD && ntt_fold_scaled(rho0, bw);
+      // same x >> (b+1) as the previous pair, and the same variant of it
+      if ((rho0 & (half - 1)) != 0 && !(FOLD && ntt_fold_scaled(ntt_pair_rho0(RK, bw, j - 1), bw))) {
         w[j] = w[j - 1];
         wp[j] = wp[j - 1];
         continue;
       }
-      if (last) {
+      if (last && (!FOLD || scaled)) {
         w[j] = a.w1n;
         wp[j] = a.w1n_p;
         continue;
@@ -468,13 +470,13 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
         w[j] = a.w1n + (xof(rho0) >> (b + 1)) + hi;
         wp[j] = a.w1n_p;
       } else if constexpr (UNIFORM) {
-        const uint32_t idx = (1u << (G0 + k)) + (hi << k) + (xof(rho0) >> (b + 1));
+        const uint32_t idx = ntt_tw_index(G0, b, hi, xof(rho0)) + (scaled ? kNttFoldBase : 0u);
         const uint32_t iu = __builtin_amdgcn_readfirstlane(idx);
         tw_put(w[j], wp[j], reinterpret_cast<const tw_t<MONT>*>(a.tw)[iu]);
       } else if constexpr (LTW && COL) {
         tw_put(w[j], wp[j], ltw[(1u << k) + (xof(rho0) >> (b + 1)) - 8u]);
       } else if constexpr (LTW) {
-        tw_put(w[j], wp[j], ltw[(k == 6 ? 32u * grp : 64u + 32u * (rho0 >> 1)) + t]);
+        tw_put(w[j], wp[j], ltw[(k == 6 ? 32u * (rho0 >> 2) : 64u + 32u * (rho0 >> 1)) + t]);
       } else if constexpr (MTW) {  // M round: COL tw[8, 64) ahead of the L round's; RP the row's stage 3-5 entries after them
         tw_put(w[j], wp[j],
                COL ? ltw[(1u << k) + (xof(rho0) >> (b + 1)) - 8u]
@@ -482,17 +484,15 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
       } else if constexpr (!COL && PAT == 2) {
         // ROW last round (stages 14, 15): lane-ordered copy after the natural table, lane t's
         // j-th twiddle at t + 32 j, so every load is one coalesced 512-B (MONT: 256-B) run
-        const uint32_t pos = (65536u + hi * 192u) + (k == 6 ? 32u * grp : 64u + 32u * (rho0 >> 1)) + t;
+        const uint32_t pos = (kNttRowCopyBase + hi * 192u) + (k == 6 ? 32u * (rho0 >> 2) : 64u + 32u * (rho0 >> 1)) + t;
         tw_put(w[j], wp[j], tw_bload<MONT>(twr, pos));
       } else {
-        const uint32_t idx = (1u << (G0 + k)) + (hi << k) + (xof(rho0) >> (b + 1));
-        tw_put(w[j], wp[j], tw_bload<MONT>(twr, idx));
+        tw_put(w[j], wp[j], tw_bload<MONT>(twr, ntt_tw_index(G0, b, hi, xof(rho0))));
       }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int grp = j / (NPK / 2), jj = j % (NPK / 2);
-      const int rho0 = grp * NPK + ((jj >> bw) << (bw + 1)) + (jj & (half - 1));
+      const int rho0 = ntt_pair_rho0(RK, bw, j);
       const int rho1 = rho0 + half;
       if constexpr ((PROBE & 2) != 0) {
         e[rho0] += e[rho1] ^ w[j] ^ wp[j];
@@ -503,7 +503,7 @@ __device__ __forceinline__ void ntt16_round(const Ntt64Args& a, __amdgpu_buffer_
         if constexpr (!INV) {
           fwd_bfly_m<SW>(e[rho0], e[rho1], w[j], a.q2, K);
         } else {
-          if (last) {
+          if (last && (!FOLD || ntt_fold_product(rho0, bw, RK))) {
             inv_bfly_m<true>(e[rho0], e[rho1], w[j], a.q2, K);
             e[rho0] = mont_x<true>(e[rho0], a.ninv, K);
           } else {
@@ -690,12 +690,166 @@ __device__ __forceinline__ void ntt16_tile(const Ntt64Args& a, uint32_t tile, ui
   }
 }
 
-template <bool MONT, bool INV, bool COL, bool SCALE, bool CANON, bool RP = false, int MINW = 1, int PROBE = 0>
-__global__ __launch_bounds__(512, MINW) void ntt16_pass(Ntt64Args a) {
-  __shared__ uint64_t lds[16 * 288];
-  __shared__ tw_t<MONT> ltw[COL || RP ? 248 : 1];  // 39.9 KiB (MONT: 37.9 KiB) per workgroup with lds: 4 per CU
+// ----------------------------------------------------------------------------------------
+// The same tile with 16 points per thread, for the two MONT passes that measured faster on it
+// (DESIGN.md section 4.2): ROW forward on RP tiles and COL inverse.  256 threads, rounds of 4 + 4
+// stages, A (window [4, 8), x = t + 16 y) and B ([0, 4), x = 16 t + r): COL has one LDS exchange
+// instead of two, ROW two with its transpose instead of three, and the butterflies are the same.
+// Round A's 15 twiddles are uniform over the tile (scalar loads), round B's 15 per lane come from
+// the tile's LDS copy (ntt_tile.hpp: ntt16_stage_src, ntt16_ltw_pos, and the LDS images).  COL
+// forward and ROW inverse measured no faster on this tile and stay on 8 points; their halves of this
+// tile are tools/experiments/ntt16_tile16_all_passes.patch.
+// ----------------------------------------------------------------------------------------
+template <int PAT, bool INV, bool SCALE, bool COL, int PROBE>
+__device__ __forceinline__ void ntt16x_round(const Ntt64Args& a, uint64_t (&e)[16], uint32_t hi, uint32_t t, MontK& K,
+                                             const uint64_t* ltw) {
+  constexpr int G0 = COL ? 0 : 8, RK = 4, LO = PAT == 0 ? 4 : 0;
+  constexpr bool TOP = INV && SCALE && COL && PAT == 0;  // the round that holds global stage 0
+  constexpr bool FOLD = TOP && (PROBE & 1) == 0;
+  constexpr bool SW = PAT == 0 && (PROBE & 1) == 0;  // twiddles in SGPRs
+#pragma unroll
+  for (int sp = 0; sp < RK; ++sp) {
+    const int bw = ntt_round_bw(INV, RK, sp);
+    const int b = LO + bw;
+    const int half = 1 << bw;
+    const bool last = TOP && b == 7;
+    uint64_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int rho0 = ntt_pair_rho0(RK, bw, j);
+      const bool scaled = FOLD && ntt_fold_scaled(rho0, bw);
+      if ((rho0 & (half - 1)) != 0 && !(FOLD && ntt_fold_scaled(ntt_pair_rho0(RK, bw, j - 1), bw))) {
+        w[j] = w[j - 1];
+        continue;
+      }
+      if (last && (!FOLD || scaled)) {
+        w[j] = a.w1n;
+        continue;
+      }
+      const uint32_t x = ntt16_xof(PAT, t, rho0);
+      if constexpr ((PROBE & 1) != 0) {
+        w[j] = a.w1n + (x >> (b + 1)) + hi;
+      } else if constexpr (PAT == 0) {
+        const uint32_t idx = ntt_tw_index(G0, b, hi, x) + (scaled ? kNttFoldBase : 0u);
+        w[j] = a.tw[__builtin_amdgcn_readfirstlane(idx)];
+      } else {
+        w[j] = ltw[ntt16_ltw_pos((1u << (7 - b)) + (x >> (b + 1)))];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int rho0 = ntt_pair_rho0(RK, bw, j);
+      const int rho1 = rho0 + half;
+      if constexpr ((PROBE & 2) != 0) {
+        e[rho0] += e[rho1] ^ w[j];
+      } else if constexpr (!INV) {
+        fwd_bfly_m<SW>(e[rho0], e[rho1], w[j], a.q2, K);
+      } else if (last && (!FOLD || ntt_fold_product(rho0, bw, RK))) {
+        inv_bfly_m<true>(e[rho0], e[rho1], w[j], a.q2, K);
+        e[rho0] = mont_x<true>(e[rho0], a.ninv, K);
+      } else {
+        inv_bfly_m<SW>(e[rho0], e[rho1], w[j], a.q2, K);
+      }
+    }
+  }
+}
+
+template <bool INV, bool COL, bool SCALE, bool CANON, int PROBE>
+__device__ __forceinline__ void ntt16x_tile(const Ntt64Args& a, uint32_t tile, uint64_t* lds, uint64_t* ltw) {
+  static_assert(INV == COL, "ROW forward and COL inverse");
+  const uint32_t tid = threadIdx.x;
+  const uint32_t s = ntt16_s_of(COL, tid), t = ntt16_t_of(COL, tid);
+  // COL: poly * 2^16 + column block * 16; ROW: row (tile & 255) of polys 16 (tile >> 8) + s
+  const size_t tbase = COL ? (((size_t)(tile >> 4) << 16) + ((tile & 15u) << 4))
+                           : (((size_t)(tile >> 8) << 20) + ((tile & 255u) << 8));
+  const __amdgpu_buffer_rsrc_t rin = rg_buf(a.in + tbase);
+  const __amdgpu_buffer_rsrc_t rout = rg_buf(a.out + tbase);
+  const uint32_t hi = COL ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane(tile & 255u);
+  uint64_t e[16];
+  // round B's 240 twiddles, one word per thread, loaded after the tile's data loads and written to
+  // LDS before the first barrier
+  const bool stv_on = (PROBE & 1) == 0 && tid < 240u;
+  const uint32_t st_src = ntt16_stage_src(COL, hi, 16u + tid), st_dst = ntt16_ltw_pos(16u + tid);
+  // global accesses, one VGPR offset per pattern.  COL: element x * 256 + s, loaded in the B
+  // pattern (rows r apart: soffset r << 11) and stored in the A pattern (rows 16 y apart: y << 15);
+  // ROW: element (s << 16) + x, both ways in the A pattern (128-B runs 16 y elements apart:
+  // immediate 128 y)
+  const uint32_t gA = COL ? ((t << 8) + s) * 8u : ((s << 16) + t) * 8u;
+  if constexpr ((PROBE & 4) != 0) {
+#pragma unroll
+    for (int y = 0; y < 16; ++y) e[y] = (uint64_t)(tid * 0x9E3779B9u + tile * 16u + (uint32_t)y);
+  } else if constexpr (COL) {
+    const uint32_t gB = ((t << 12) + s) * 8u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) e[r] = rg_bload(rin, gB, (uint32_t)r << 11);
+  } else {
+#pragma unroll
+    for (int y = 0; y < 16; ++y) e[y] = rg_bload(rin, gA + 128u * y, 0);
+  }
+  uint64_t stv = 0;
+  if (stv_on) stv = a.tw[st_src];
+  const uint32_t pA = ntt16_lds_pos(COL, s, t), pB = ntt16_lds_pos(COL, s, 16u * t);
+  constexpr int oA = COL ? 272 : 17, oB = COL ? 16 : 1;
+  MontK K = mont_k(a.q1);
+  if constexpr (!INV) {  // ROW forward
+    ntt16x_round<0, false, false, COL, PROBE>(a, e, hi, t, K, ltw);
+    if (stv_on) ltw[st_dst] = stv;
+#pragma unroll
+    for (int y = 0; y < 16; ++y) lds[pA + oA * y] = e[y];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) e[r] = lds[pB + oB * r];
+    ntt16x_round<1, false, false, COL, PROBE>(a, e, hi, t, K, ltw);
+    if (CANON) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) e[r] = canon_x(e[r], a.q);
+    }
+    __syncthreads();  // B -> A through LDS, then 128-B runs
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lds[pB + oB * r] = e[r];
+    __syncthreads();
+#pragma unroll
+    for (int y = 0; y < 16; ++y) e[y] = lds[pA + oA * y];
+  } else {  // COL inverse
+    if (stv_on) ltw[st_dst] = stv;
+    __syncthreads();  // the staged twiddles
+    ntt16x_round<1, true, SCALE, COL, PROBE>(a, e, hi, t, K, ltw);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lds[pB + oB * r] = e[r];
+    __syncthreads();
+#pragma unroll
+    for (int y = 0; y < 16; ++y) e[y] = lds[pA + oA * y];
+    ntt16x_round<0, true, SCALE, COL, PROBE>(a, e, hi, t, K, ltw);
+    if (CANON) {
+#pragma unroll
+      for (int y = 0; y < 16; ++y) e[y] = canon_x(e[y], a.q);
+    }
+  }
+#pragma unroll
+  for (int y = 0; y < 16; ++y) {
+    const uint32_t vo = COL ? gA : gA + 128u * y, so = COL ? (uint32_t)y << 15 : 0u;
+    if constexpr ((PROBE & 4) != 0) {  // the result stays live through a store that never fires
+      if (e[y] == ~0ull) rg_bstore(e[y], rout, vo, so);
+    } else {
+      rg_bstore(e[y], rout, vo, so);
+    }
+  }
+}
+
+// PTS: points per thread, 8 (512 threads) or 16 (256 threads; MONT, ROW forward on RP tiles or COL inverse)
+template <bool MONT, bool INV, bool COL, bool SCALE, bool CANON, bool RP = false, int MINW = 1, int PTS = 8, int PROBE = 0>
+__global__ __launch_bounds__(PTS == 16 ? 256 : 512, MINW) void ntt16_pass(Ntt64Args a) {
   const uint32_t tile = a.rev ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
-  ntt16_tile<MONT, INV, COL, SCALE, CANON, RP, PROBE>(a, tile, lds, ltw);
+  if constexpr (PTS == 16) {
+    static_assert(MONT && INV == COL && (COL || RP), "the 16-point tile serves MONT ROW forward (RP) and COL inverse");
+    __shared__ uint64_t lds[kNtt16LdsLen];
+    __shared__ uint64_t ltw[kNtt16LtwLen];  // 35.9 KiB per workgroup with lds: 4 per CU
+    ntt16x_tile<INV, COL, SCALE, CANON, PROBE>(a, tile, lds, ltw);
+  } else {
+    __shared__ uint64_t lds[16 * 288];
+    __shared__ tw_t<MONT> ltw[COL || RP ? 248 : 1];  // 39.9 KiB (MONT: 37.9 KiB) per workgroup with lds: 4 per CU
+    ntt16_tile<MONT, INV, COL, SCALE, CANON, RP, PROBE>(a, tile, lds, ltw);
+  }
 }
 
 #endif  // __HIPCC__

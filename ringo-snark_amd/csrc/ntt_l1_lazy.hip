@@ -10,18 +10,32 @@
 namespace rg {
 
 // ROW passes tile the same row of 16 polynomials when the chunk allows it (RP, twiddles
-// shared by the whole tile); otherwise 16 consecutive rows of one polynomial
+// shared by the whole tile); otherwise 16 consecutive rows of one polynomial.  tile16: the plan's
+// choice (NttLaunch::tile16) for the two MONT passes that have a 16-point tile, ROW forward on RP
+// tiles and COL inverse: 256 threads and at most 128 VGPRs, so that four workgroups share a CU as
+// they do on 8 points
 template <bool MONT, bool INV, bool COL, bool SCALE, bool CANON>
-static rg_status launch64m(const Ntt64Args& a, size_t polys, hipStream_t st) {
+static rg_status launch64m(const Ntt64Args& a, size_t polys, bool tile16, hipStream_t st) {
   const long long tiles = a.total_sub / 16;
-  if (measure_probe() == 4) {  // bench.py's compute floor (rg_set_probe, experiments build): no HBM data movement
-    if (!COL && polys % 16 == 0)
-      hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, true, 1, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
+  const bool rp = !COL && polys % 16 == 0;
+  const bool probe = measure_probe() == 4;  // bench.py's compute floor (rg_set_probe, experiments build): no HBM data movement
+  if constexpr (MONT && INV == COL) {
+    if (tile16 && (COL || rp)) {
+      if (probe)
+        hipLaunchKernelGGL((ntt16_pass<true, INV, COL, SCALE, CANON, !COL, 4, 16, 4>), dim3((unsigned)tiles), dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL((ntt16_pass<true, INV, COL, SCALE, CANON, !COL, 4, 16>), dim3((unsigned)tiles), dim3(256), 0, st, a);
+      return check_launch(probe ? "ntt16_pass (16 points, probe)" : "ntt16_pass (16 points)");
+    }
+  }
+  if (probe) {
+    if (rp)
+      hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, true, 1, 8, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
     else
-      hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, false, 1, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
+      hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, false, 1, 8, 4>), dim3((unsigned)tiles), dim3(512), 0, st, a);
     return check_launch("ntt16_pass (probe)");
   }
-  if (!COL && polys % 16 == 0)
+  if (rp)
     hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, true>), dim3((unsigned)tiles), dim3(512), 0, st, a);
   else
     hipLaunchKernelGGL((ntt16_pass<MONT, INV, COL, SCALE, CANON, false>), dim3((unsigned)tiles), dim3(512), 0, st, a);
@@ -29,8 +43,9 @@ static rg_status launch64m(const Ntt64Args& a, size_t polys, hipStream_t st) {
 }
 
 template <bool INV, bool COL, bool SCALE, bool CANON>
-static rg_status launch64(const Ntt64Args& a, bool mont, size_t polys, hipStream_t st) {
-  return mont ? launch64m<true, INV, COL, SCALE, CANON>(a, polys, st) : launch64m<false, INV, COL, SCALE, CANON>(a, polys, st);
+static rg_status launch64(const Ntt64Args& a, const NttLaunch& p, size_t polys, hipStream_t st) {
+  return p.mont ? launch64m<true, INV, COL, SCALE, CANON>(a, polys, p.tile16, st)
+                : launch64m<false, INV, COL, SCALE, CANON>(a, polys, false, st);
 }
 
 rg_status ntt64_run(const NttLaunch& p, hipStream_t st) {
@@ -55,18 +70,18 @@ rg_status ntt64_run(const NttLaunch& p, hipStream_t st) {
     a.rev = 0;
     if (!p.inv) {
       a.G0 = 0;
-      RG_TRY((launch64<false, true, false, false>(a, p.mont, nb, st)));
+      RG_TRY((launch64<false, true, false, false>(a, p, nb, st)));
       a.in = a.out;
       a.G0 = 8;
       a.rev = 1;  // reverse tile order: reads what the first pass wrote last first (ntt64.hpp)
-      RG_TRY((launch64<false, false, false, true>(a, p.mont, nb, st)));
+      RG_TRY((launch64<false, false, false, true>(a, p, nb, st)));
     } else {
       a.G0 = 8;
-      RG_TRY((launch64<true, false, false, false>(a, p.mont, nb, st)));
+      RG_TRY((launch64<true, false, false, false>(a, p, nb, st)));
       a.in = a.out;
       a.G0 = 0;
       a.rev = 1;  // reverse tile order: reads what the first pass wrote last first (ntt64.hpp)
-      RG_TRY((launch64<true, true, true, true>(a, p.mont, nb, st)));
+      RG_TRY((launch64<true, true, true, true>(a, p, nb, st)));
     }
   }
   return RG_OK;

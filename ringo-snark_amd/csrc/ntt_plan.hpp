@@ -25,6 +25,7 @@ struct NttLaunch : NttRouting {  // the direction's route, table format and pass
   uint64_t w1n_sh;
   int logN;
   size_t chunk_polys;  // Tiled (two passes), Lazy64: polynomials per pass pair
+  bool tile16;         // Lazy64: ROW forward (RP) / COL inverse on 16 points per thread (ntt_route.hpp)
   struct Aux* aux;  // Fast256: the plan's helper stream for the two-half split; else null
 };
 

@@ -27,6 +27,12 @@ constexpr int kMinTiledP = 6;
 constexpr uint32_t kMontMaxQ1 = 0x47e0f66au;
 constexpr bool ntt64_mont_ok(uint64_t q) { return (uint32_t)q == 1u && (q >> 32) != 0 && (q >> 32) <= kMontMaxQ1; }
 
+// Lazy64 with the Montgomery product: whether a direction's 16-point pass (ntt64.hpp: ROW forward
+// on RP tiles, batch % 16 == 0; COL inverse) runs on the tile of 16 points per thread (rounds of
+// 4 + 4 stages, one LDS exchange fewer) or, like every other pass and every Shoup plan, on 8 points
+// (3 + 3 + 2).  sw: the NttKernel switch of the experiments build or null; t8 keeps 8 points.
+inline bool ntt64_tile16(bool mont, const char* sw) { return mont && !(sw && sw[0] == 't' && sw[1] == '8'); }
+
 enum class NttRoute : int {
   Stages,   // ntt_stage_kernel, one launch per stage: whatever the others leave
   Tiled,    // ntt_pass_kernel / ntt_r2 / ntt_r8, LDS-tiled: L <= 4, kMinTiledP <= logN <= 2 pmax
