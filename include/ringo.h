@@ -156,6 +156,23 @@ rg_status rg_poly_evaluate_batch_dev(const rg_field* f, const uint64_t* d_p, siz
                                      const uint64_t* d_x, uint64_t* d_out, void* d_scratch, void* stream);
 rg_status rg_poly_evaluate_batch(const rg_field* f, const uint64_t* p, size_t n, size_t stride, size_t batch,
                                  const uint64_t* x, uint64_t* out);
+/* The same with a point per group of polynomials: polynomial b is evaluated at point
+ * (b / group) % n_points, and point p is the element at d_x + p * x_stride * L words.  A buffer
+ * laid out [proof][slot] takes group = slots per proof; one laid out [slot][proof] takes group = 1
+ * and n_points = proofs (the index wraps).  The kernels are those of rg_poly_evaluate_batch_dev, each
+ * reading the power tables of its polynomial's point; the tables of all points come from two
+ * rg_buckler_powers_batch_dev calls, so the launch count (4) does not depend on n_points, and
+ * n_points = 1 gives the limbs of rg_poly_evaluate_batch_dev.  d_scratch holds
+ * rg_poly_evaluate_multi_scratch_bytes(f, n, batch, n_points) bytes.  RG_ERR_INVALID for group = 0,
+ * n_points = 0 or x_stride = 0, for more than 65535 points in use (points beyond the last group are
+ * never read) and for what rg_poly_evaluate_batch_dev refuses.  The host form reads
+ * (n_points - 1) * x_stride + 1 elements of x. */
+size_t rg_poly_evaluate_multi_scratch_bytes(const rg_field* f, size_t n, size_t batch, size_t n_points);
+rg_status rg_poly_evaluate_multi_dev(const rg_field* f, const uint64_t* d_p, size_t n, size_t stride, size_t batch,
+                                     const uint64_t* d_x, size_t x_stride, size_t n_points, size_t group,
+                                     uint64_t* d_out, void* d_scratch, void* stream);
+rg_status rg_poly_evaluate_multi(const rg_field* f, const uint64_t* p, size_t n, size_t stride, size_t batch,
+                                 const uint64_t* x, size_t x_stride, size_t n_points, size_t group, uint64_t* out);
 /* CyclotomicEvaluator.ModSwitchTo(pOut, pBig, qBig) (cyclotomic.go:97-124) on n coefficients:
  * pBig[i] as w little-endian words of a two's-complement integer ([n][w], |pBig[i]| < 2^(64w-1);
  * Go's big.Int values, e.g. PolyToBigintCentered output), qBig as w words (host, 0 < qBig <
@@ -244,9 +261,28 @@ rg_status rg_buckler_checker_transpose_dev(const rg_linchecker* c, uint64_t* d_o
                                            void* stream);
 rg_status rg_buckler_checker_transform(const rg_linchecker* c, uint64_t* out, const uint64_t* v);
 rg_status rg_buckler_checker_transpose(const rg_linchecker* c, uint64_t* out, const uint64_t* v);
+/* TransposeTo of a projection checker with a matrix per vector: vector i of d_v [batch][rank][L] is
+ * transposed by the matrix packed from the 32 * rank XOF bytes at d_xof + i * 32 * rank (each proof
+ * draws its own from projConst, prover.go:165-176).  The checker's own matrix is neither read nor
+ * changed, so a checker that was never set is accepted and calls on several streams are independent.
+ * d_bits_scratch holds rg_buckler_checker_transpose_xof_scratch_bytes(c, batch) bytes (16 per column
+ * and vector).  RG_ERR_INVALID for a checker of another kind, a NULL or aliased buffer, or batch >
+ * 65535. */
+size_t rg_buckler_checker_transpose_xof_scratch_bytes(const rg_linchecker* c, size_t batch);
+rg_status rg_buckler_checker_transpose_xof_dev(const rg_linchecker* c, uint64_t* d_out, const uint64_t* d_v,
+                                               size_t batch, const uint8_t* d_xof, void* d_bits_scratch,
+                                               void* stream);
 /* linCheckVec (prover.go:409-413): out[0] = SetUint64(1), out[i] = out[i-1] * c, n elements. */
 rg_status rg_buckler_powers_dev(const rg_field* f, const uint64_t* d_c, size_t n, uint64_t* d_out, void* stream);
 rg_status rg_buckler_powers(const rg_field* f, const uint64_t* c, size_t n, uint64_t* out);
+/* The power tables of n_c bases in one launch: out[k][i] = c_k^i for k < n_c, i < n, with base k at
+ * d_c + k * c_stride * L words and d_out [n_c][n][L].  n_c = 0 or n = 0 does nothing; c_stride = 0
+ * or n_c > 65535 (a base per grid row) is RG_ERR_INVALID.  The host form reads
+ * (n_c - 1) * c_stride + 1 elements of c. */
+rg_status rg_buckler_powers_batch_dev(const rg_field* f, const uint64_t* d_c, size_t c_stride, size_t n_c, size_t n,
+                                      uint64_t* d_out, void* stream);
+rg_status rg_buckler_powers_batch(const rg_field* f, const uint64_t* c, size_t c_stride, size_t n_c, size_t n,
+                                  uint64_t* out);
 /* Prover.sumCheckMask(maskRank) (prover.go:381-397) from the mask_rank injected draws d_rand, in
  * the order the reference draws them: mask[k] = r[k] - r[k+rank] while k + rank < mask_rank, r[k]
  * up to mask_rank, zero up to emb_rank; maskSum = r[0].  rank <= mask_rank <= emb_rank, and d_rand
@@ -357,6 +393,40 @@ rg_status rg_buckler_verify_checks_dev(const rg_bverifier* v, const uint64_t* d_
 rg_status rg_buckler_verify_checks(const rg_bverifier* v, const uint64_t* evals, const uint64_t* pw,
                                    const uint64_t* chal, const uint64_t* mask_sums, uint64_t* verdict,
                                    uint64_t* sides, uint64_t* pw_evals);
+/* n_proofs proofs of one compiled circuit (one handle) decided by one call whose launch count does
+ * not depend on n_proofs.  Every per-proof argument is proof-major and has the single entry's
+ * meaning per proof: d_evals [n_proofs][n_evals][L], d_pw [n_proofs][n_pw][rank][L] (NULL iff n_pw =
+ * 0), d_chal [n_proofs][5][L], d_mask_sums [n_proofs][2][L], d_verdict [n_proofs] words (the bits
+ * above, per proof), optional d_sides [n_proofs][8][L] and d_pw_evals [n_proofs][n_pw][L].
+ * d_xof [n_proofs][32 * rank] bytes: the XOF bytes of each proof's projection matrix (prover.go:165-176).
+ * Every projection checker of the handle uses the proof's one matrix, as the reference's single
+ * ctx.projChecker does; the checkers' own matrices are neither read nor changed.  d_xof is required
+ * iff the handle's linear check holds a projection checker and must be NULL otherwise.
+ *
+ * The pipeline: one rg_buckler_powers_batch_dev of every proof's linCheckConst, each checker's
+ * transpose over all proofs in one call (rg_buckler_checker_transpose_xof_dev for a projection
+ * checker), one kernel placing the public witnesses beside them, ONE batched InvNTT over all
+ * n_proofs * (1 + n_chk + n_pw) vectors, ONE rg_poly_evaluate_multi_dev at the proofs' evalPoints
+ * and ONE launch of the decision kernel with a workgroup per proof.  Each output word has one
+ * writer; nothing is copied back and nothing is waited for inside.
+ *
+ * n_proofs = 0 does nothing.  RG_ERR_INVALID for n_proofs > RG_BK_MULTI_MAX_PROOFS (a proof per grid
+ * row of the power-table and projection kernels), for n_proofs * (1 + n_chk + n_pw) > 2^30 vectors or
+ * more than 2^39 words in them (grid extents and byte offsets), and for what the single entry refuses;
+ * every argument is validated before the device is touched and no buffer may alias another.
+ * d_scratch holds rg_buckler_verify_checks_multi_scratch_bytes(v, n_proofs) bytes (0 for an n_proofs
+ * that is refused); calls on different streams use different scratch.  The form without `_dev`
+ * takes host pointers and is synchronous. */
+#define RG_BK_MULTI_MAX_PROOFS 65535
+size_t rg_buckler_verify_checks_multi_scratch_bytes(const rg_bverifier* v, size_t n_proofs);
+rg_status rg_buckler_verify_checks_multi_dev(const rg_bverifier* v, size_t n_proofs, const uint64_t* d_evals,
+                                             const uint64_t* d_pw, const uint8_t* d_xof, const uint64_t* d_chal,
+                                             const uint64_t* d_mask_sums, uint64_t* d_verdict, uint64_t* d_sides,
+                                             uint64_t* d_pw_evals, uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_verify_checks_multi(const rg_bverifier* v, size_t n_proofs, const uint64_t* evals,
+                                         const uint64_t* pw, const uint8_t* xof, const uint64_t* chal,
+                                         const uint64_t* mask_sums, uint64_t* verdict, uint64_t* sides,
+                                         uint64_t* pw_evals);
 
 /* ---- Buckler norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---- */
 /* decomposeBig on the device: a Montgomery element w is taken out of Montgomery form, centred

@@ -29,6 +29,7 @@ namespace rg {
 constexpr int kProjRows = 128;   // linear.go:99
 constexpr int kProjChunk = 128;  // columns per workgroup of the projection transform
 constexpr int kPowBlock = 16;    // exponents per lane of the power vector
+constexpr size_t kMaxGridY = 65535;  // the y extent of a grid: the entries with an item per blockIdx.y refuse more
 
 // ---- NTT checker: vOut[i] = v[rank-1-i] * scale (linear.go:39-41) ------------------------------
 template <int L>
@@ -45,10 +46,13 @@ __global__ __launch_bounds__(256) void revscale_kernel(FieldParams<L> F, Elem<L>
 
 // ---- projection checker ---------------------------------------------------------------------
 // bits[j][w] = ~(bytes 4w .. 4w+3 of column j's 32 XOF bytes, little-endian), w < 4: bit i % 32 of
-// word i / 32 is bit i % 8 of byte i / 8, set iff the XOF bit is 0 (prover.go:171-176)
+// word i / 32 is bit i % 8 of byte i / 8, set iff the XOF bit is 0 (prover.go:171-176).  Matrix
+// blockIdx.y: bits [.][rank][4] from xof [.][rank][32]
 __global__ __launch_bounds__(256) void proj_pack_kernel(uint32_t* bits, const uint8_t* xof, long long rank) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= rank * 4) return;
+  bits += (long long)blockIdx.y * rank * 4;
+  xof += (long long)blockIdx.y * rank * 32;
   const long long j = gid >> 2;
   const int w = (int)(gid & 3);
   const uint8_t* s = xof + j * 32 + 4 * w;
@@ -107,13 +111,17 @@ __global__ __launch_bounds__(256) void proj_sum_kernel(FieldParams<L> F, uint64_
   el_copy<L>(out + gid * L, acc);
 }
 
-// TransposeTo (linear.go:125-137): a lane per column, v[0..127] in LDS
+// TransposeTo (linear.go:125-137): a lane per column, v[0..127] in LDS.  Vector b = blockIdx.y reads
+// the matrix at bits + b * bits_stride words: 0 for the checker's one matrix, rank * 4 for a matrix
+// per vector
 template <int L>
 __global__ __launch_bounds__(kProjRows) void proj_tr_kernel(FieldParams<L> F, uint64_t* out, const uint64_t* v,
-                                                             const uint32_t* bits, long long rank) {
+                                                             const uint32_t* bits, long long bits_stride,
+                                                             long long rank) {
   __shared__ uint64_t sv[kProjRows * L];
   const int tid = threadIdx.x;
   const long long b = blockIdx.y, j = (long long)blockIdx.x * kProjRows + tid;
+  bits += b * bits_stride;
   el_copy<L>(sv + tid * L, v + (b * rank + tid) * L);  // rank >= 128
   __syncthreads();
   if (j >= rank) return;
@@ -175,12 +183,15 @@ __global__ __launch_bounds__(256) void recompose_tr_kernel(FieldParams<L> F, uin
 }
 
 // ---- power vector (prover.go:409-413) ---------------------------------------------------------
+// base blockIdx.y at c + blockIdx.y * c_stride words, its table at out + blockIdx.y * n elements
 template <int L>
 __global__ __launch_bounds__(256) void powers_kernel(FieldParams<L> F, Elem<L> one, const uint64_t* c,
-                                                     uint64_t* out, long long n) {
+                                                     long long c_stride, uint64_t* out, long long n) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long e0 = t * kPowBlock;
   if (e0 >= n) return;
+  c += (long long)blockIdx.y * c_stride;
+  out += (long long)blockIdx.y * n * L;
   uint64_t cv[L], p[L], sq[L];
   el_copy<L>(cv, c);
   el_copy<L>(p, one.v);
@@ -302,9 +313,10 @@ static rg_status proj_fwd_L(const rg_linchecker* c, uint64_t* out, const uint64_
 }
 
 template <int L>
-static rg_status proj_tr_L(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
+static rg_status proj_tr_L(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch,
+                           const uint32_t* bits, long long bits_stride, hipStream_t st) {
   hipLaunchKernelGGL(proj_tr_kernel<L>, dim3((unsigned)proj_chunks(c->rank), (unsigned)batch), dim3(kProjRows), 0, st,
-                     field_params<L>(&c->f), out, v, c->bits.as<uint32_t>(), c->rank);
+                     field_params<L>(&c->f), out, v, bits, bits_stride, c->rank);
   return check_launch("proj transpose");
 }
 
@@ -321,10 +333,11 @@ static rg_status recompose_L(const rg_linchecker* c, bool tr, uint64_t* out, con
 }
 
 template <int L>
-static rg_status powers_L(const rg_field* f, const uint64_t* c, long long n, uint64_t* out, hipStream_t st) {
+static rg_status powers_L(const rg_field* f, const uint64_t* c, long long c_stride, long long n_c, long long n,
+                          uint64_t* out, hipStream_t st) {
   const long long lanes = (n + kPowBlock - 1) / kPowBlock;
-  hipLaunchKernelGGL(powers_kernel<L>, dim3(grid256(lanes)), dim3(256), 0, st, field_params<L>(f), elem<L>(f->one), c,
-                     out, n);
+  hipLaunchKernelGGL(powers_kernel<L>, dim3(grid256(lanes), (unsigned)n_c), dim3(256), 0, st, field_params<L>(f),
+                     elem<L>(f->one), c, c_stride * L, out, n);
   return check_launch("powers");
 }
 
@@ -387,8 +400,9 @@ static rg_status proj_fwd(const rg_linchecker* c, uint64_t* out, const uint64_t*
                           hipStream_t st) {
   return dispatch_limbs(c->f.L, [&](auto Lc) { return proj_fwd_L<Lc()>(c, out, v, batch, scratch, st); });
 }
-static rg_status proj_tr(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch, hipStream_t st) {
-  return dispatch_limbs(c->f.L, [&](auto Lc) { return proj_tr_L<Lc()>(c, out, v, batch, st); });
+static rg_status proj_tr(const rg_linchecker* c, uint64_t* out, const uint64_t* v, long long batch,
+                         const uint32_t* bits, long long bits_stride, hipStream_t st) {
+  return dispatch_limbs(c->f.L, [&](auto Lc) { return proj_tr_L<Lc()>(c, out, v, batch, bits, bits_stride, st); });
 }
 static rg_status recompose(const rg_linchecker* c, bool tr, uint64_t* out, const uint64_t* v, long long batch,
                            hipStream_t st) {
@@ -415,7 +429,8 @@ static rg_status checker_apply(const rg_linchecker* c, bool tr, uint64_t* d_out,
                              stream);
     case RG_CHK_PROJ:
       if (!c->bits_set || (!tr && !d_scratch)) return RG_ERR_INVALID;
-      return tr ? proj_tr(c, d_out, d_v, nb, st) : proj_fwd(c, d_out, d_v, nb, d_scratch, st);
+      return tr ? proj_tr(c, d_out, d_v, nb, c->bits.as<uint32_t>(), 0, st)
+                : proj_fwd(c, d_out, d_v, nb, d_scratch, st);
     case RG_CHK_RECOMPOSE: return recompose(c, tr, d_out, d_v, nb, st);
     default: return RG_ERR_INVALID;
   }
@@ -547,6 +562,29 @@ rg_status rg_buckler_checker_transform(const rg_linchecker* c, uint64_t* out, co
   return checker_host(c, false, out, v);
 }
 
+// ---- projection transpose with a matrix per vector (the verifier's batch of proofs) ---------------
+size_t rg_buckler_checker_transpose_xof_scratch_bytes(const rg_linchecker* c, size_t batch) {
+  if (!c || c->kind != RG_CHK_PROJ) return 0;
+  return batch * (size_t)c->rank * 16;
+}
+
+rg_status rg_buckler_checker_transpose_xof_dev(const rg_linchecker* c, uint64_t* d_out, const uint64_t* d_v,
+                                               size_t batch, const uint8_t* d_xof, void* d_bits_scratch,
+                                               void* stream) {
+  if (!c || c->kind != RG_CHK_PROJ || !d_out || !d_v || d_out == d_v) return RG_ERR_INVALID;
+  if (batch > kMaxGridY) return RG_ERR_INVALID;  // a vector per blockIdx.y
+  if (batch == 0) return RG_OK;
+  if (!d_xof || !d_bits_scratch || d_bits_scratch == (const void*)d_out || d_bits_scratch == (const void*)d_v ||
+      d_bits_scratch == (const void*)d_xof)
+    return RG_ERR_INVALID;
+  hipStream_t st = as_stream(stream);
+  uint32_t* bits = reinterpret_cast<uint32_t*>(d_bits_scratch);
+  hipLaunchKernelGGL(proj_pack_kernel, dim3(grid256(c->rank * 4), (unsigned)batch), dim3(256), 0, st, bits, d_xof,
+                     c->rank);
+  RG_TRY(check_launch("proj pack"));
+  return proj_tr(c, d_out, d_v, (long long)batch, bits, c->rank * 4, st);
+}
+
 rg_status rg_buckler_checker_transpose(const rg_linchecker* c, uint64_t* out, const uint64_t* v) {
   return checker_host(c, true, out, v);
 }
@@ -556,7 +594,31 @@ rg_status rg_buckler_powers_dev(const rg_field* f, const uint64_t* d_c, size_t n
   if (!f || !d_c || (n && !d_out) || d_out == d_c || n > ((size_t)1 << 40)) return RG_ERR_INVALID;
   if (n == 0) return RG_OK;
   hipStream_t st = as_stream(stream);
-  return dispatch_limbs(f->L, [&](auto Lc) { return powers_L<Lc()>(f, d_c, (long long)n, d_out, st); });
+  return dispatch_limbs(f->L, [&](auto Lc) { return powers_L<Lc()>(f, d_c, 1, 1, (long long)n, d_out, st); });
+}
+
+rg_status rg_buckler_powers_batch_dev(const rg_field* f, const uint64_t* d_c, size_t c_stride, size_t n_c, size_t n,
+                                      uint64_t* d_out, void* stream) {
+  if (!f || n > ((size_t)1 << 40) || n_c > kMaxGridY) return RG_ERR_INVALID;  // a base per blockIdx.y
+  if (n_c == 0 || n == 0) return RG_OK;
+  if (!d_c || !d_out || d_out == d_c || c_stride == 0 || c_stride > ((size_t)1 << 30)) return RG_ERR_INVALID;
+  hipStream_t st = as_stream(stream);
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    return powers_L<Lc()>(f, d_c, (long long)c_stride, (long long)n_c, (long long)n, d_out, st);
+  });
+}
+
+rg_status rg_buckler_powers_batch(const rg_field* f, const uint64_t* c, size_t c_stride, size_t n_c, size_t n,
+                                  uint64_t* out) {
+  if (!f || n > ((size_t)1 << 40) || n_c > kMaxGridY) return RG_ERR_INVALID;
+  if (n_c == 0 || n == 0) return RG_OK;
+  if (!c || !out || c_stride == 0 || c_stride > ((size_t)1 << 30)) return RG_ERR_INVALID;
+  const size_t e = (size_t)f->L * 8;
+  DevBuf dc, dout;
+  RG_TRY(dc.upload(c, ((n_c - 1) * c_stride + 1) * e));
+  RG_TRY(dout.alloc(n_c * n * e));
+  RG_TRY(rg_buckler_powers_batch_dev(f, dc.as<uint64_t>(), c_stride, n_c, n, dout.as<uint64_t>(), nullptr));
+  return dout.download(out, n_c * n * e);
 }
 
 rg_status rg_buckler_powers(const rg_field* f, const uint64_t* c, size_t n, uint64_t* out) {

@@ -10,6 +10,11 @@
 //     219-315 -- vanishEval, the remLo shift, evalCircuit on scalars for both constraint lists, the
 //     linear check's chain, the five comparisons -- so no field element goes to the host between
 //     the stages.
+//   * a batch of proofs of one handle (rg_buckler_verify_checks_multi_dev): the same stages over
+//     scratch laid out [vector][proof][rank] -- one power table of every proof's linCheckConst, each
+//     checker's transpose over all proofs (a projection checker with each proof's own matrix), the
+//     public witnesses placed by place_pw_kernel, ONE InvNTT, ONE Evaluate with a point per proof and
+//     ONE verify_decide_kernel launch with a workgroup per proof: the launch count has no n_proofs.
 // Every value is a canonical Montgomery residue (field.hpp), so a sum or product regrouped exactly
 // in the field has the reference's limbs.  Three regroupings are used, each an identity of the field:
 //   sum_c (bc * ev_c)                    = bc * sum_c ev_c                 (evalCircuit, one bc for all c)
@@ -57,6 +62,10 @@ struct DecideArgs {
   unsigned long long rank, shift_exp;
   int n_lin_vec, n_pw;
   int i_lin_mask, i_sum_mask, i_arith_quo, i_lin_quo, i_sum_quo;
+  // Workgroup p decides proof p.  Words from one proof's evals, challenges, mask sums, sides and
+  // pw_out to the next proof's, and from one vector's evaluation in `ev` to the next vector's of the
+  // same proof (`ev` is [vector][proof][L]; proof p's first is at ev + p L).  The verdict stride is 1.
+  unsigned long long evals_stride, chal_stride, mask_stride, sides_stride, pw_out_stride, ev_stride;
 };
 
 // The sum of every lane's acc, folded through LDS in a fixed tree (lane i takes i + s for s = 128,
@@ -88,8 +97,16 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
   __shared__ uint32_t bits[3];
   const int tid = threadIdx.x;
   const bool has_a = a.circ[0].nc >= 0, has_l = a.pair_off != nullptr, has_s = a.circ[1].nc >= 0;
+  const size_t proof = blockIdx.x;
+  a.evals += proof * a.evals_stride;
+  a.ev += proof * L;
+  a.chal += proof * a.chal_stride;
+  a.mask_sums += proof * a.mask_stride;
+  a.verdict += proof;
+  if (a.sides) a.sides += proof * a.sides_stride;
+  if (a.pw_out) a.pw_out += proof * a.pw_out_stride;
   const uint64_t* x = a.chal;
-  const uint64_t* pw_ev = a.ev + (size_t)a.n_lin_vec * L;
+  const uint64_t* pw_ev = a.ev + (size_t)a.n_lin_vec * a.ev_stride;
 
   // ---- the powers (bignum.Exp).  A lane's tasks: first, on lanes 64, 128 and 192 only,
   // evalPoint^rank - 1, evalPoint^(jindo_rank - (rank - 1)) or sumCheckBatchConst^2 -- one wave
@@ -122,7 +139,7 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
         int c = 0;
         while (c + 1 < a.n_chk && (uint32_t)t >= a.pair_off[c + 1]) ++c;  // the pair's checker
         uint64_t term[L], u[L], w[L];
-        el_copy<L>(u, a.ev + (size_t)(1 + c) * L);
+        el_copy<L>(u, a.ev + (size_t)(1 + c) * a.ev_stride);
         el_copy<L>(w, a.evals + (size_t)a.pairs[2 * t + 1] * L);
         f_mul<L>(term, u, w, a.F);  // term.Mul(linCheckTrEval, wIn)
         el_copy<L>(u, a.ev);
@@ -162,7 +179,7 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
         const uint32_t k0 = wit_off[t], k1 = wit_off[t + 1];
 #pragma unroll 1
         for (long long k = (pi >= 0) ? (long long)k0 - 1 : (long long)k0; k < (long long)k1; ++k) {
-          const uint64_t* src = (k < (long long)k0) ? pw_ev + (size_t)pi * L : a.evals + (size_t)wit[k] * L;
+          const uint64_t* src = (k < (long long)k0) ? pw_ev + (size_t)pi * a.ev_stride : a.evals + (size_t)wit[k] * L;
           el_copy<L>(y, src);
           f_mul<L>(term, term, y, a.F);  // term.Mul(term, pwEvals[...]) / term.Mul(term, evals[...])
         }
@@ -246,7 +263,7 @@ __global__ __launch_bounds__(kDecideLanes) void verify_decide_kernel(DecideArgs<
     }
   }
   if (a.pw_out)
-    for (int i = tid; i < a.n_pw * L; i += kDecideLanes) a.pw_out[i] = pw_ev[i];
+    for (int i = tid; i < a.n_pw * L; i += kDecideLanes) a.pw_out[i] = pw_ev[(size_t)(i / L) * a.ev_stride + i % L];
   __syncthreads();
   if (tid == 0) a.verdict[0] = (uint64_t)(bits[0] | bits[1] | bits[2]);
 }
@@ -257,9 +274,9 @@ static rg_status bv_invalid(const std::string& why) {
 }
 
 template <int L>
-static rg_status decide_L(const rg_bverifier* v, const uint64_t* evals, const uint64_t* ev, const uint64_t* chal,
-                          const uint64_t* mask_sums, uint64_t* verdict, uint64_t* sides, uint64_t* pw_out,
-                          hipStream_t st) {
+static rg_status decide_L(const rg_bverifier* v, size_t n_proofs, const uint64_t* evals, const uint64_t* ev,
+                          const uint64_t* chal, const uint64_t* mask_sums, uint64_t* verdict, uint64_t* sides,
+                          uint64_t* pw_out, hipStream_t st) {
   const rg_field* f = ntt_field(v->enc);
   DecideArgs<L> a;
   a.F = field_params<L>(f);
@@ -287,12 +304,54 @@ static rg_status decide_L(const rg_bverifier* v, const uint64_t* evals, const ui
   a.i_arith_quo = v->i_arith_quo;
   a.i_lin_quo = v->i_lin_quo;
   a.i_sum_quo = v->i_sum_quo;
-  hipLaunchKernelGGL(verify_decide_kernel<L>, dim3(1), dim3(kDecideLanes), 0, st, a);
+  a.evals_stride = (unsigned long long)v->n_evals * L;
+  a.chal_stride = 5 * L;
+  a.mask_stride = 2 * L;
+  a.sides_stride = 8 * L;
+  a.pw_out_stride = (unsigned long long)v->n_pw * L;
+  a.ev_stride = (unsigned long long)n_proofs * L;
+  hipLaunchKernelGGL(verify_decide_kernel<L>, dim3((unsigned)n_proofs), dim3(kDecideLanes), 0, st, a);
   return check_launch("buckler verify decide");
 }
 
 // scratch (elements of L words): vec [n_vec][rank] | ev [n_vec] | the batched evaluate's scratch
 static size_t bv_n_vec(const rg_bverifier* v) { return v->n_lin_vec + v->n_pw; }
+
+// ---- a batch of proofs ---------------------------------------------------------------------------
+// The public witnesses of every proof beside the linear check's vectors: pw [proof][j][rank][L] ->
+// out [j][proof][rank][L], a word per lane, both sides read and written in runs.
+__global__ __launch_bounds__(256) void place_pw_kernel(uint64_t* out, const uint64_t* pw, unsigned long long vec_words,
+                                                       unsigned long long n_pw, unsigned long long n_proofs) {
+  const unsigned long long gid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= vec_words * n_pw * n_proofs) return;
+  const unsigned long long w = gid % vec_words, pj = gid / vec_words;  // pj = proof * n_pw + j
+  const unsigned long long p = pj / n_pw, j = pj % n_pw;
+  out[(j * n_proofs + p) * vec_words + w] = pw[gid];
+}
+
+static bool bv_has_proj(const rg_bverifier* v) {
+  if (v->lin)
+    for (const rg_linchecker* c : v->lin->chk)
+      if (c->kind == RG_CHK_PROJ) return true;
+  return false;
+}
+
+// n_proofs the batch entry takes: RG_BK_MULTI_MAX_PROOFS (a proof per blockIdx.y of the power-table
+// and projection kernels), and few enough that the n_proofs * n_vec vectors are at most 2^30
+// polynomials (the batched evaluate's range) of at most 2^39 words in all: a lane per word fits a
+// 1-D grid of 256-lane blocks and every byte offset stays far below 2^63
+static bool bv_proofs_ok(const rg_bverifier* v, size_t n_proofs) {
+  if (n_proofs > RG_BK_MULTI_MAX_PROOFS) return false;
+  const size_t polys = bv_n_vec(v) * n_proofs;  // < 2^22 * 2^16
+  return polys <= ((size_t)1 << 30) && polys * (size_t)v->rank <= (((size_t)1 << 39) / ntt_field(v->enc)->L);
+}
+
+// scratch of the batch entry (elements of L words): vec [n_vec][n_proofs][rank] | ev [n_vec][n_proofs] |
+// the evaluate's scratch | the packed projection matrices [n_proofs][rank] x 16 bytes (with a
+// projection checker)
+static size_t bv_multi_eval_scratch(const rg_bverifier* v, size_t n_proofs) {
+  return rg_poly_evaluate_multi_scratch_bytes(ntt_field(v->enc), (size_t)v->rank, bv_n_vec(v) * n_proofs, n_proofs);
+}
 
 }  // namespace rg
 
@@ -395,7 +454,7 @@ rg_status rg_buckler_verify_checks_dev(const rg_bverifier* v, const uint64_t* d_
     RG_TRY(rg_poly_evaluate_batch_dev(f, vec, rank, rank, nv, d_chal, ev, ev_scr, stream));  // Evaluate(evalPoint)
   }
   return dispatch_limbs(f->L, [&](auto Lc) {
-    return decide_L<Lc()>(v, d_evals, ev, d_chal, d_mask_sums, d_verdict, d_sides, d_pw_evals, st);
+    return decide_L<Lc()>(v, 1, d_evals, ev, d_chal, d_mask_sums, d_verdict, d_sides, d_pw_evals, st);
   });
 }
 
@@ -422,6 +481,103 @@ rg_status rg_buckler_verify_checks(const rg_bverifier* v, const uint64_t* evals,
   RG_TRY(dvd.download(verdict, 8));
   if (sides) RG_TRY(dsd.download(sides, 8 * e));
   if (dpe.p) RG_TRY(dpe.download(pw_evals, v->n_pw * e));
+  return RG_OK;
+}
+
+// ---- n_proofs proofs of one handle in one call ------------------------------------------------
+size_t rg_buckler_verify_checks_multi_scratch_bytes(const rg_bverifier* v, size_t n_proofs) {
+  if (!v || n_proofs == 0 || !bv_proofs_ok(v, n_proofs)) return 0;
+  const size_t nv = bv_n_vec(v), L = ntt_field(v->enc)->L;
+  return nv * n_proofs * ((size_t)v->rank + 1) * L * 8 + bv_multi_eval_scratch(v, n_proofs) +
+         (bv_has_proj(v) ? n_proofs * (size_t)v->rank * 16 : 0);
+}
+
+// the argument rules both forms share, before any device call
+static rg_status bv_multi_check(const rg_bverifier* v, size_t n_proofs, const void* evals, const void* pw,
+                                const void* xof, const void* chal, const void* mask_sums, const void* verdict) {
+  if (!v) return bv_invalid("NULL handle");
+  if (!bv_proofs_ok(v, n_proofs))
+    return bv_invalid("n_proofs " + std::to_string(n_proofs) + " is over the limit (RG_BK_MULTI_MAX_PROOFS, 2^39 words)");
+  if (n_proofs == 0) return RG_OK;
+  if (!evals || !chal || !verdict) return bv_invalid("NULL evals, challenges or verdict");
+  if ((v->lin || v->sum) && !mask_sums) return bv_invalid("NULL mask sums");
+  if ((pw == nullptr) != (v->n_pw == 0)) return bv_invalid("d_pw is NULL iff n_pw = 0");
+  if ((xof == nullptr) == bv_has_proj(v))
+    return bv_invalid("d_xof is required with a projection checker in the linear check and NULL without one");
+  return RG_OK;
+}
+
+rg_status rg_buckler_verify_checks_multi_dev(const rg_bverifier* v, size_t n_proofs, const uint64_t* d_evals,
+                                             const uint64_t* d_pw, const uint8_t* d_xof, const uint64_t* d_chal,
+                                             const uint64_t* d_mask_sums, uint64_t* d_verdict, uint64_t* d_sides,
+                                             uint64_t* d_pw_evals, uint64_t* d_scratch, void* stream) {
+  RG_TRY(bv_multi_check(v, n_proofs, d_evals, d_pw, d_xof, d_chal, d_mask_sums, d_verdict));
+  if (n_proofs == 0) return RG_OK;
+  const size_t nv = bv_n_vec(v);
+  if (nv && !d_scratch) return bv_invalid("NULL scratch");
+  const void* bufs[] = {d_evals, d_pw, d_xof, d_chal, d_mask_sums, d_verdict, d_sides, d_pw_evals, d_scratch};
+  for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; ++i)
+    for (size_t j = i + 1; j < sizeof bufs / sizeof bufs[0]; ++j)
+      if (bufs[i] && bufs[i] == bufs[j]) return bv_invalid("two buffers alias");
+  const rg_field* f = ntt_field(v->enc);
+  const size_t L = f->L, rank = (size_t)v->rank, np = n_proofs;
+  hipStream_t st = as_stream(stream);
+  uint64_t* vec = d_scratch;  // [n_vec][n_proofs][rank]
+  uint64_t* ev = vec + nv * np * rank * L;
+  uint64_t* ev_scr = ev + nv * np * L;
+  void* bits = reinterpret_cast<char*>(ev_scr) + bv_multi_eval_scratch(v, np);
+  if (v->lin) {
+    // every proof's linCheckVec (verifier.go:258-262): linCheckConst is challenge 3 of 5
+    RG_TRY(rg_buckler_powers_batch_dev(f, d_chal + 3 * L, 5, np, rank, vec, stream));
+    for (size_t c = 0; c < v->lin->chk.size(); ++c) {  // tr.TransposeTo(linCheckVecTr, linCheckVec), all proofs
+      const rg_linchecker* chk = v->lin->chk[c];
+      uint64_t* out = vec + (1 + c) * np * rank * L;
+      if (chk->kind == RG_CHK_PROJ)  // the proof's own matrix (prover.go:165-176), not the handle's
+        RG_TRY(rg_buckler_checker_transpose_xof_dev(chk, out, vec, np, d_xof, bits, stream));
+      else
+        RG_TRY(rg_buckler_checker_transpose_dev(chk, out, vec, np, stream));
+    }
+  }
+  if (v->n_pw) {
+    const unsigned long long words = (unsigned long long)rank * L;
+    hipLaunchKernelGGL(place_pw_kernel, dim3(grid256((long long)(words * v->n_pw * np))), dim3(256), 0, st,
+                       vec + v->n_lin_vec * np * rank * L, d_pw, words, (unsigned long long)v->n_pw,
+                       (unsigned long long)np);
+    RG_TRY(check_launch("buckler verify place pw"));
+  }
+  if (nv) {
+    RG_TRY(rg_ntt_inv_dev(v->enc, vec, vec, nv * np, stream));  // Encode of every vector of every proof
+    // vector s of proof p is polynomial s * n_proofs + p: group 1, point p = the proof's evalPoint
+    RG_TRY(rg_poly_evaluate_multi_dev(f, vec, rank, rank, nv * np, d_chal, 5, np, 1, ev, ev_scr, stream));
+  }
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    return decide_L<Lc()>(v, np, d_evals, ev, d_chal, d_mask_sums, d_verdict, d_sides, d_pw_evals, st);
+  });
+}
+
+rg_status rg_buckler_verify_checks_multi(const rg_bverifier* v, size_t n_proofs, const uint64_t* evals,
+                                         const uint64_t* pw, const uint8_t* xof, const uint64_t* chal,
+                                         const uint64_t* mask_sums, uint64_t* verdict, uint64_t* sides,
+                                         uint64_t* pw_evals) {
+  RG_TRY(bv_multi_check(v, n_proofs, evals, pw, xof, chal, mask_sums, verdict));
+  if (n_proofs == 0) return RG_OK;
+  const size_t e = (size_t)ntt_field(v->enc)->L * 8, np = n_proofs;
+  DevBuf dev, dpw, dxo, dch, dms, dvd, dsd, dpe, dscr;
+  RG_TRY(dev.upload(evals, np * v->n_evals * e));
+  if (v->n_pw) RG_TRY(dpw.upload(pw, np * v->n_pw * (size_t)v->rank * e));
+  if (xof) RG_TRY(dxo.upload(xof, np * (size_t)v->rank * 32));
+  RG_TRY(dch.upload(chal, np * 5 * e));
+  if (mask_sums) RG_TRY(dms.upload(mask_sums, np * 2 * e));
+  RG_TRY(dvd.alloc(np * 8));
+  if (sides) RG_TRY(dsd.alloc(np * 8 * e));
+  if (pw_evals && v->n_pw) RG_TRY(dpe.alloc(np * v->n_pw * e));
+  RG_TRY(dscr.alloc(rg_buckler_verify_checks_multi_scratch_bytes(v, np)));
+  RG_TRY(rg_buckler_verify_checks_multi_dev(v, np, dev.as<uint64_t>(), dpw.as<uint64_t>(), dxo.as<uint8_t>(),
+                                            dch.as<uint64_t>(), dms.as<uint64_t>(), dvd.as<uint64_t>(),
+                                            dsd.as<uint64_t>(), dpe.as<uint64_t>(), dscr.as<uint64_t>(), nullptr));
+  RG_TRY(dvd.download(verdict, np * 8));
+  if (sides) RG_TRY(dsd.download(sides, np * 8 * e));
+  if (dpe.p) RG_TRY(dpe.download(pw_evals, np * v->n_pw * e));
   return RG_OK;
 }
 

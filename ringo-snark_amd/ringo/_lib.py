@@ -86,6 +86,11 @@ _SIGS = {
                                                   vp]),
     "rg_poly_evaluate_batch": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p,
                                               u64p]),
+    "rg_poly_evaluate_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t]),
+    "rg_poly_evaluate_multi_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp,
+                                                  ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp]),
+    "rg_poly_evaluate_multi": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p,
+                                              ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p]),
     "rg_poly_modswitch_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, u64p, vp, vp]),
     "rg_poly_modswitch": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p]),
     "rg_buckler_encode_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp, vp, vp]),
@@ -113,8 +118,12 @@ _SIGS = {
     "rg_buckler_checker_transpose_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp]),
     "rg_buckler_checker_transform": (ctypes.c_int, [vp, u64p, u64p]),
     "rg_buckler_checker_transpose": (ctypes.c_int, [vp, u64p, u64p]),
+    "rg_buckler_checker_transpose_xof_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_buckler_checker_transpose_xof_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
     "rg_buckler_powers_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, vp]),
     "rg_buckler_powers": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, u64p]),
+    "rg_buckler_powers_batch_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),
+    "rg_buckler_powers_batch": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p]),
     "rg_buckler_sumcheck_mask_dev": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp,
                                                     vp]),
     "rg_buckler_sumcheck_mask": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p,
@@ -140,6 +149,9 @@ _SIGS = {
     "rg_buckler_verify_checks_scratch_bytes": (ctypes.c_size_t, [vp]),
     "rg_buckler_verify_checks_dev": (ctypes.c_int, [vp] * 10),
     "rg_buckler_verify_checks": (ctypes.c_int, [vp] + [u64p] * 7),
+    "rg_buckler_verify_checks_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_buckler_verify_checks_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t] + [vp] * 10),
+    "rg_buckler_verify_checks_multi": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p, ctypes.c_char_p] + [u64p] * 5),
     "rg_buckler_dcmp_create": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.POINTER(vp)]),
     "rg_buckler_dcmp_destroy": (None, [vp]),
     "rg_buckler_dcmp_inf_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),

@@ -462,6 +462,48 @@ def EvaluateBatch(polys, x):
     return out
 
 
+def evaluate_multi_scratch_bytes(field, n, batch, n_points):
+    """Bytes of device scratch evaluate_multi_dev needs (rg_poly_evaluate_multi_scratch_bytes)."""
+    return lib().rg_poly_evaluate_multi_scratch_bytes(field.h, n, batch, n_points)
+
+
+def evaluate_multi_dev(field, d_p, n, stride, batch, d_x, x_stride, n_points, group, d_out, d_scratch, stream=None):
+    """rg_poly_evaluate_multi_dev: evaluate_batch_dev with a point per group of polynomials.
+    Polynomial b is evaluated at point (b // group) % n_points; point p is the element at
+    d_x + p * x_stride * L words.  d_scratch of evaluate_multi_scratch_bytes."""
+    if stride < n or group <= 0 or n_points <= 0 or x_stride <= 0:
+        raise RingoPanic("inconsistent input(s)")
+    L = field.L
+    pw = ((batch - 1) * stride + n) * L if batch and n else None
+    sw = (evaluate_multi_scratch_bytes(field, n, batch, n_points) + 7) // 8
+    used = min(n_points, -(-batch // group)) if batch else 1  # the points the call reads
+    check(lib().rg_poly_evaluate_multi_dev(field.h, _addr(d_p, pw) if n else _addr(d_p), n, stride, batch,
+                                           _addr(d_x, ((used - 1) * x_stride + 1) * L), x_stride, n_points, group,
+                                           _addr(d_out, batch * L), _addr(d_scratch, sw), _stream(stream)))
+
+
+def EvaluateMulti(polys, xs, group):
+    """[p_b.Evaluate(xs[(b // group) % len(xs)]) for b, p_b in enumerate(polys)] in one call
+    (rg_poly_evaluate_multi): polys of one field and rank, coefficient domain; xs [n_points][L];
+    returns [len(polys)][L]."""
+    polys = list(polys)
+    if not polys or group <= 0:
+        raise RingoPanic("inconsistent input(s)")
+    field, n = polys[0].field, polys[0].Rank()
+    for p in polys:
+        if p.IsNTT:
+            raise RingoPanic("Evaluate: p is in NTT form")
+        if p.Rank() != n or p.field.L != field.L:
+            raise RingoPanic("inconsistent input(s)")
+    xx = np.ascontiguousarray(xs, np.uint64).reshape(-1, field.L)
+    if xx.shape[0] == 0:
+        raise RingoPanic("inconsistent input(s)")
+    co = np.ascontiguousarray(np.stack([p.Coeffs for p in polys]), np.uint64)
+    out = np.zeros((len(polys), field.L), np.uint64)
+    check(lib().rg_poly_evaluate_multi(field.h, ptr(co), n, n, len(polys), ptr(xx), 1, xx.shape[0], group, ptr(out)))
+    return out
+
+
 def vec_dev(field, op, d_out, d_a, d_b, n, stream=None):
     """rg_vec_dev: device-resident pointwise op over n elements."""
     w = n * field.L

@@ -23,6 +23,12 @@ and the norm decomposition of the witness assignment (buckler/utils.go:34-56, pr
     digits = dc.DecomposeInf(w)                                # [nb][rank][L], one witness per digit
     wDcmp = dc.DecomposeProj(wProj)                            # second round, prover.go:182-192
     wDcmp, sqNm = dc.DecomposeTwoNorm(w); pwBase, pwMask = TwoNormPublic(F, rank, bound)
+
+and the verifier's checks (buckler/verifier.go:178-315), one proof or a batch of proofs of one circuit:
+
+    plan = VerifyPlan(F, rank, jindoRank, wCnt, nPw, lin, arith, sum)
+    verdict, sides, pwEvals = plan.checks(evals, pw, chal, maskSums)
+    verdicts, sides, pwEvals = plan.checks_multi(evals, pw, xof, chal, maskSums)   # [n] in front of each
 """
 import ctypes
 
@@ -316,6 +322,27 @@ class ProjChecker(LinearChecker):
         _status(lib().rg_buckler_checker_set_xof_dev(self.h, d_xof, _stream(stream)))
         return self
 
+    def transpose_xof_scratch_bytes(self, batch):
+        return lib().rg_buckler_checker_transpose_xof_scratch_bytes(self.h, batch)
+
+    def transpose_xof_dev(self, d_out, d_v, batch, d_xof, d_bits_scratch, stream=None):
+        """rg_buckler_checker_transpose_xof_dev: vector i of [batch][rank][L] transposed by the matrix
+        of the XOF bytes d_xof[i] ([batch][rank * 32] uint8); the checker's own matrix is not used."""
+        w = batch * self.rank * self.field.L
+        _status(lib().rg_buckler_checker_transpose_xof_dev(
+            self.h, _addr(d_out, w), _addr(d_v, w), batch, _xof_addr(d_xof, batch * self.rank * 32),
+            _addr(d_bits_scratch, self.transpose_xof_scratch_bytes(batch) // 8), _stream(stream)))
+
+
+def _xof_addr(d_xof, nbytes):
+    """Device address of a contiguous uint8 tensor of at least nbytes (or an address)."""
+    if d_xof is None or isinstance(d_xof, int):
+        return d_xof
+    if str(d_xof.dtype) != "torch.uint8" or not d_xof.is_contiguous() or d_xof.device.type != "cuda" \
+            or d_xof.numel() < nbytes:
+        raise RingoPanic(f"XOF buffer: need {nbytes} contiguous bytes on the GPU")
+    return d_xof.data_ptr()
+
 
 class ProjRecomposeChecker(LinearChecker):
     """newProjRecomposeChecker (linear.go:144-153): dcmpBase = decomposeBase(bound) as field elements."""
@@ -339,6 +366,24 @@ def Powers(field, c, n):
 
 def powers_dev(field, d_c, n, d_out, stream=None):
     _status(lib().rg_buckler_powers_dev(field.h, _addr(d_c, field.L), n, _addr(d_out, n * field.L), _stream(stream)))
+
+
+def PowersBatch(field, cs, n, c_stride=1):
+    """rg_buckler_powers_batch: out[k][i] = c_k^i, [n_c][n][L]; cs holds base k at element k * c_stride."""
+    cs = np.ascontiguousarray(np.asarray(cs, np.uint64).reshape(-1, field.L))
+    if c_stride <= 0 or cs.shape[0] == 0:
+        raise RingoPanic("inconsistent input(s)")
+    n_c = (cs.shape[0] - 1) // c_stride + 1
+    out = np.zeros((n_c, n, field.L), np.uint64)
+    _status(lib().rg_buckler_powers_batch(field.h, ptr(cs), c_stride, n_c, n, ptr(out)))
+    return out
+
+
+def powers_batch_dev(field, d_c, c_stride, n_c, n, d_out, stream=None):
+    """rg_buckler_powers_batch_dev: base k at d_c + k * c_stride * L words, d_out [n_c][n][L]."""
+    L = field.L
+    _status(lib().rg_buckler_powers_batch_dev(field.h, _addr(d_c, ((n_c - 1) * c_stride + 1) * L if n_c else None),
+                                              c_stride, n_c, n, _addr(d_out, n_c * n * L), _stream(stream)))
 
 
 def SumCheckMask(field, rank, maskRank, embRank, rand):
@@ -553,6 +598,45 @@ class VerifyPlan:
         _status(lib().rg_buckler_verify_checks(self.h, ptr(ev), ptr(pwa), ptr(ch), ptr(ms), ptr(verdict), ptr(sides),
                                                ptr(pwe)))
         return int(verdict[0]), sides, pwe[:self.nPw]
+
+    def scratch_bytes_multi(self, n_proofs):
+        return lib().rg_buckler_verify_checks_multi_scratch_bytes(self.h, n_proofs)
+
+    def checks_multi_dev(self, n_proofs, d_evals, d_pw, d_xof, d_chal, d_mask_sums, d_verdict, d_sides=None,
+                         d_pw_evals=None, d_scratch=None, stream=None):
+        """rg_buckler_verify_checks_multi_dev: checks_dev for n_proofs proofs of this plan in one call,
+        every buffer proof-major ([n_proofs] in front of checks_dev's shapes); d_xof [n_proofs][rank * 32]
+        uint8, each proof's projection matrix (None iff the linear check has no projection checker);
+        d_verdict n_proofs words.  Asynchronous on `stream`."""
+        L, n = self.field.L, n_proofs
+        opt = lambda t, w: _addr(t, w) if t is not None else None  # noqa: E731
+        _status(lib().rg_buckler_verify_checks_multi_dev(
+            self.h, n, _addr(d_evals, n * self.n_evals * L), opt(d_pw, n * self.nPw * self.rank * L),
+            _xof_addr(d_xof, n * self.rank * 32), _addr(d_chal, n * 5 * L), opt(d_mask_sums, n * 2 * L),
+            _addr(d_verdict, n), opt(d_sides, n * 8 * L), opt(d_pw_evals, n * self.nPw * L),
+            opt(d_scratch, self.scratch_bytes_multi(n) // 8), _stream(stream)))
+
+    def checks_multi(self, evals, pw, xof, chal, maskSums):
+        """rg_buckler_verify_checks_multi (host arrays, synchronous): evals [n][n_evals][L], pw
+        [n][nPw][rank][L] (None iff nPw = 0), xof n * rank * 32 bytes or None, chal [n][5][L], maskSums
+        [n][2][L] -> (verdicts [n], sides [n][8][L], pwEvals [n][nPw][L])."""
+        L = self.field.L
+        ev = np.ascontiguousarray(np.asarray(evals, np.uint64).reshape(-1, self.n_evals, L))
+        n = ev.shape[0]
+        arr = lambda a, k: None if a is None else np.ascontiguousarray(np.asarray(a, np.uint64).reshape(n, k, L))  # noqa: E731
+        ch, ms = arr(chal, 5), arr(maskSums, 2)
+        pwa = None if self.nPw == 0 else np.ascontiguousarray(
+            np.asarray(pw, np.uint64).reshape(n, self.nPw, self.rank, L))
+        if xof is not None:
+            xof = bytes(xof)
+            if len(xof) < n * self.rank * 32:
+                raise RingoPanic("index out of range")
+        verdict = np.full(max(n, 1), 2 ** 64 - 1, np.uint64)
+        sides = np.full((max(n, 1), 8, L), 2 ** 64 - 1, np.uint64)
+        pwe = np.full((max(n, 1), max(self.nPw, 1), L), 2 ** 64 - 1, np.uint64)
+        _status(lib().rg_buckler_verify_checks_multi(self.h, n, ptr(ev), ptr(pwa), xof, ptr(ch), ptr(ms), ptr(verdict),
+                                                     ptr(sides), ptr(pwe)))
+        return [int(x) for x in verdict[:n]], sides[:n], pwe[:n, :self.nPw]
 
 
 def VerifyChecks(field, rank, jindoRank, wCnt, challenges, maskSums, evals, pw, checkers, linConstraints,

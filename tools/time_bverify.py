@@ -9,9 +9,14 @@ the embedding rank 2^16 and one rg_poly_evaluate_dev, then the nine evaluations 
 stream waited for (host clock around the loop, since the copy back ends every call); the scalar
 algebra that would follow on the host is not in that figure.
 
+With --proofs N[,N...] the script times instead, per N and alternating in one process, a loop of N
+rg_buckler_verify_checks_dev calls (one proof each, one scratch) against ONE
+rg_buckler_verify_checks_multi_dev of the same N proofs, `--runs` times each, and prints one line per
+leg and run with the time per proof and the scratch bytes; the composition leg is skipped.
+
 The launch counts are counted from the code (csrc/buckler_verify.hip and the entries it calls), not
 measured.  The values are random: a timing, not a proof.
-usage: python tools/time_bverify.py [--iters 200] [--warmup 20] [--rank 32768]"""
+usage: python tools/time_bverify.py [--iters 200] [--warmup 20] [--rank 32768] [--proofs 1,8,64 [--runs 3]]"""
 import argparse
 import json
 import os
@@ -30,6 +35,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=20)
 ap.add_argument("--rank", type=int, default=1 << 15)
+ap.add_argument("--proofs", type=str, default="", help="comma-separated batch sizes for the batch-entry leg")
+ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
 
 assert torch.cuda.is_available(), "time_bverify.py needs the GPU"
@@ -84,6 +91,55 @@ print(json.dumps({"entry": "rg_buckler_verify_checks_dev", "field": "jindo_zp", 
                   "pairs": 4, "n_pw": n_pw, "iters": args.iters, "ms_per_call": round(ms, 5),
                   "kernel_launches_per_call": sum(parts.values()), "launches": parts, "d2d_copies_per_call": 1}),
       flush=True)
+
+# ---- N proofs: a loop of single calls against one batch call -----------------------------------------
+def timed(fn, iters):
+    with torch.cuda.stream(stream):
+        for _ in range(args.warmup):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(iters):
+            fn()
+        e1.record(stream)
+    e1.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def proofs_leg(n):
+    """n proofs with every input different but the XOF bytes, which are the checker's own for every proof
+    so that both ways compute the same thing; they must leave the same verdicts and pwEvals."""
+    m_evals, m_chal, m_ms = dev(n * plan.n_evals).reshape(n, -1, L), dev(n * 5).reshape(n, 5, L), dev(n * 2).reshape(n, 2, L)
+    m_pw = dev(n * n_pw * rank).reshape(n, n_pw, rank, L)
+    m_xof = torch.from_numpy(np.frombuffer(rng.bytes(32 * rank), np.uint8).copy()).cuda().repeat(n, 1)  # the checker's
+    v1, v2 = (torch.zeros(n, dtype=torch.int64, device="cuda") for _ in range(2))
+    pe1, pe2 = (torch.zeros((n, n_pw, L), dtype=torch.int64, device="cuda") for _ in range(2))
+    chks[2].set_xof_dev(m_xof[0])
+    torch.cuda.synchronize()
+    mscr = torch.empty(plan.scratch_bytes_multi(n) // 8, dtype=torch.int64, device="cuda")
+
+    def loop():
+        for i in range(n):
+            plan.checks_dev(m_evals[i], m_pw[i], m_chal[i], m_ms[i], v1[i:i + 1], None, pe1[i], scr, stream=stream)
+
+    def multi():
+        plan.checks_multi_dev(n, m_evals, m_pw, m_xof, m_chal, m_ms, v2, None, pe2, mscr, stream=stream)
+
+    for run in range(args.runs):
+        for name, fn, bytes_ in (("loop of rg_buckler_verify_checks_dev", loop, plan.scratch_bytes()),
+                                 ("rg_buckler_verify_checks_multi_dev", multi, plan.scratch_bytes_multi(n))):
+            t = timed(fn, args.iters)
+            print(json.dumps({"entry": name, "proofs": n, "run": run, "iters": args.iters, "rank": rank, "L": L,
+                              "ms_per_batch": round(t, 5), "us_per_proof": round(t * 1e3 / n, 3),
+                              "scratch_bytes": bytes_}), flush=True)
+    torch.cuda.synchronize()
+    assert (v1.cpu() == v2.cpu()).all() and (pe1.cpu() == pe2.cpu()).all(), "the two ways differ"
+
+
+if args.proofs:
+    for n_proofs in (int(x) for x in args.proofs.split(",")):
+        proofs_leg(n_proofs)
+    sys.exit(0)
 
 # ---- the composition of existing entries, one vector at a time ---------------------------------------
 lib = _lib.lib()
