@@ -714,6 +714,42 @@ rg_status rg_jindo_verify_dev(const rg_jindo* j, size_t batch, const uint64_t* d
                               const uint64_t* d_pf_partial, const uint64_t* d_pf_enc, const uint64_t* d_pf_mlwe,
                               double in_com_dcmp_two_nm, double res_two_nm, rg_jindo_verify_result* res,
                               void* stream);
+/* n_proofs proofs against one handle verified by one enqueue: the Jindo counterpart of
+ * rg_buckler_verify_checks_multi_dev, to be queued behind it on the same stream.  Every array
+ * argument of rg_jindo_verify_dev gains a leading [n_proofs] dimension, proof-major and contiguous
+ * (d_com [n_proofs][batch][out_msis][nq][d], d_chals [n_proofs][cols][nq][d], d_left
+ * [n_proofs][rows][nq][d], d_right [n_proofs][cols*slots][L], d_y [n_proofs][batch][L], ...): each
+ * proof has its own transcript, hence its own challenges and evaluation point.  `batch` and the two
+ * bounds hold for all proofs; d_bq and d_bo are both NULL iff batch == 1.
+ *
+ * d_out [n_proofs][RG_JINDO_VERIFY_WORDS] receives one record per proof, every word written:
+ *   word 0      ok (1 or 0)
+ *   word 1      bit 0 outer_ok, bit 1 inner_ok, bit 2 consistency_ok, bit 3 eval_ok
+ *   words 2-11  outer_norm_sq        words 12-21  inner_norm_sq
+ *   words 22-37 eval_lhs: L words, the rest 0
+ *   words 38-53 eval_rhs: L words, the rest 0 (batch == 1: y[0], as the single entry reports it)
+ * with the single entry's values, the norm decisions included (made on the device against K^2 of each
+ * bound).  rg_jindo_verify_unpack (host only) turns one record into an rg_jindo_verify_result;
+ * RG_ERR_INVALID for a NULL argument or a field_limbs no kernel is built for.
+ *
+ * Asynchronous on `stream`: nothing is allocated, freed, copied to the host or waited for inside, and
+ * the number of launches does not depend on n_proofs.  The handle is only read, so calls on different
+ * streams with different scratch are independent.  d_scratch holds
+ * rg_jindo_verify_multi_scratch_bytes(j, n_proofs, batch) bytes (0 for a NULL handle, an n_proofs of 0
+ * or above RG_JINDO_VERIFY_MAX_PROOFS -- a proof per grid row -- or batch < 1).
+ * RG_ERR_INVALID, with the reason in rg_last_error and before the device is touched: a NULL handle,
+ * input, output or scratch; n_proofs of 0 or above the limit; batch < 1; the d_bq / d_bo rule; d_out
+ * or d_scratch overlapping an input or each other. */
+#define RG_JINDO_VERIFY_MAX_PROOFS 65535
+#define RG_JINDO_VERIFY_WORDS 54 /* uint64 words per proof record */
+size_t rg_jindo_verify_multi_scratch_bytes(const rg_jindo* j, size_t n_proofs, size_t batch);
+rg_status rg_jindo_verify_multi_dev(const rg_jindo* j, size_t n_proofs, size_t batch, const uint64_t* d_com,
+                                    const uint64_t* d_bq, const uint64_t* d_bo, const uint64_t* d_chals,
+                                    const uint64_t* d_left, const uint64_t* d_right, const uint64_t* d_y,
+                                    const uint64_t* d_pf_incom, const uint64_t* d_pf_partial,
+                                    const uint64_t* d_pf_enc, const uint64_t* d_pf_mlwe, double in_com_dcmp_two_nm,
+                                    double res_two_nm, uint64_t* d_out, void* d_scratch, void* stream);
+rg_status rg_jindo_verify_unpack(const uint64_t* words, int field_limbs, rg_jindo_verify_result* res);
 
 /* ------------------------------------------------------------------------------------ */
 /* Device memory helpers (so a cgo caller needs no HIP headers)                           */

@@ -211,6 +211,191 @@ __global__ __launch_bounds__(256) void dot2_kernel(FieldParams<L> F, const uint6
 }
 
 // ------------------------------------------------------------------------------------------
+// A batch of proofs of one handle (rg_jindo_verify_multi_dev).  The kernels above take every
+// proof's polynomials in one launch as they are; the commit-key MACs run on mac_kernel with a
+// column per proof.  The products whose two operands both belong to the proof (MacArgs has no
+// per-column stride for A) and the per-proof decisions are these:
+//   pdot_kernel         thread per (proof, output, limb * d + coeff): a J = 1 dot product with a proof
+//                       stride on both operands and on the optional addend
+//   consistency_kernel  thread per (proof, limb * d + coeff): both sides of verifyConsistency, never
+//                       stored; a difference ORs the proof's flag
+//   dot2_multi_kernel   dot2_kernel with a workgroup per proof
+//   verdict_kernel      wave per proof: the two norm sums against their thresholds, the evaluation
+//                       sides, the consistency flag -> the proof's record
+// In the first two blockIdx.y is the proof (RG_JINDO_VERIFY_MAX_PROOFS = the grid's y extent).
+// ------------------------------------------------------------------------------------------
+template <bool WIDE>
+__device__ __forceinline__ uint64_t pdot(const uint64_t* A, long long a_term, const uint64_t* B, long long b_term,
+                                         int T, const RnsPrime& P) {
+  Acc<WIDE> acc;
+  acc.zero();
+#pragma unroll 4
+  for (int t = 0; t < T; ++t) acc.mac(A[t * a_term], B[t * b_term]);
+  return acc.reduce(P);
+}
+
+struct PDotArgs {
+  int d, nl, T, nout;  // degree, limbs, terms, outputs per proof
+  const uint64_t* A;   // term t of proof p at p * a_proof + t * a_term
+  long long a_proof, a_term;
+  const uint64_t* B;   // term t of output o of proof p at p * b_proof + o * b_out + t * b_term
+  long long b_proof, b_out, b_term;
+  const uint64_t* C;   // added after reduction (nullable): p * c_proof + o * c_out
+  long long c_proof, c_out;
+  uint64_t* out;       // [proof][nout][nl][d]
+  RnsPrime P[kMaxQ];
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void pdot_kernel(PDotArgs a) {
+  const uint32_t per_col = (uint32_t)(a.nl * a.d);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint32_t)a.nout * per_col) return;
+  const uint32_t o = i / per_col, lk = i % per_col;
+  const long long p = blockIdx.y;
+  const RnsPrime& P = a.P[lk / a.d];
+  uint64_t r = pdot<WIDE>(a.A + p * a.a_proof + lk, a.a_term, a.B + p * a.b_proof + o * a.b_out + lk, a.b_term, a.T, P);
+  if (a.C) r = mod_add(a.C[p * a.c_proof + o * a.c_out + lk], r, P.q);
+  a.out[(p * a.nout + o) * per_col + lk] = r;
+}
+
+struct ConsArgs {
+  int d, nl, rows, cols;
+  const uint64_t *left, *enc;       // [proof][rows][nl][d]
+  const uint64_t *chals, *partial;  // [proof][cols][nl][d], [proof][cols + 1][nl][d]
+  int* flag;                        // [proof], zero on entry
+  RnsPrime P[kMaxQ];
+};
+
+// sum_i left[i] * Encode[i] != sum_i chals[i] * Partial[i] + PartialMask at any (limb, coeff)
+template <bool WIDE>
+__global__ __launch_bounds__(256) void consistency_kernel(ConsArgs a) {
+  const long long per_col = (long long)a.nl * a.d;
+  const long long lk = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lk >= per_col) return;
+  const long long p = blockIdx.y;
+  const RnsPrime& P = a.P[(int)(lk / a.d)];
+  const long long e0 = p * a.rows * per_col + lk;
+  const uint64_t* part = a.partial + p * (a.cols + 1) * per_col + lk;
+  const uint64_t lhs = pdot<WIDE>(a.left + e0, per_col, a.enc + e0, per_col, a.rows, P);
+  uint64_t rhs = pdot<WIDE>(a.chals + p * a.cols * per_col + lk, per_col, part, per_col, a.cols, P);
+  rhs = mod_add(part[a.cols * per_col], rhs, P.q);
+  if (lhs != rhs) atomicOr(a.flag + p, 1);
+}
+
+// dot2_kernel for workgroup = proof: operand k of proof p starts p * s_k elements in, out [proof][2][L]
+template <int L>
+__global__ __launch_bounds__(256) void dot2_multi_kernel(FieldParams<L> F, const uint64_t* x1, long long s_x1,
+                                                         const uint64_t* y1, long long s_y1, long long n1,
+                                                         const uint64_t* x2, const uint64_t* y2, long long n2,
+                                                         uint64_t* out) {
+  __shared__ uint64_t red[256 * L];
+  const long long p = blockIdx.x;
+  for (int which = 0; which < 2; ++which) {
+    const uint64_t* x = which ? x2 + p * n2 * L : x1 + p * s_x1 * L;
+    const uint64_t* y = which ? y2 + p * n2 * L : y1 + p * s_y1 * L;
+    const long long n = which ? n2 : n1;
+    uint64_t acc[L], t[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) acc[j] = 0;
+    for (long long i = threadIdx.x; i < n; i += blockDim.x) {
+      f_mul<L>(t, x + i * L, y + i * L, F);
+      f_add<L>(acc, acc, t, F);
+    }
+    el_copy<L>(red + threadIdx.x * L, acc);
+    __syncthreads();
+    for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) f_add<L>(red + threadIdx.x * L, red + threadIdx.x * L, red + (threadIdx.x + s) * L, F);
+      __syncthreads();
+    }
+    if (threadIdx.x < L) out[(p * 2 + which) * L + threadIdx.x] = red[threadIdx.x];
+    __syncthreads();
+  }
+}
+
+// a norm bound as norm_threshold built it: always = 0: S < k2; -1: no sum is below; +1: every sum is
+struct NormBound {
+  uint64_t k2[kNormW];
+  int always;
+};
+
+constexpr int kVerdictSegs = 5;  // norm rows of pf_incom, C_out | pf_enc, pf_mlwe, C_in
+constexpr int kVerdictOuter = 2;
+static_assert(RG_JINDO_VERIFY_WORDS == 2 + 2 * kNormW + 2 * 16, "ok, flags, two norm sums, two 16-word sides");
+
+struct VerdictArgs {
+  int L;
+  const uint64_t* norms[kVerdictSegs];  // [proof][cnt][kNormW] each
+  int cnt[kVerdictSegs];
+  NormBound bound[2];                   // outer, inner
+  const uint64_t* lhs;                  // eval sides: element of proof p at p * stride
+  const uint64_t* rhs;
+  long long lhs_stride, rhs_stride;
+  const int* flag;                      // [proof] verifyConsistency's difference
+  uint64_t* out;                        // [proof][RG_JINDO_VERIFY_WORDS]
+};
+
+__global__ __launch_bounds__(64) void verdict_kernel(VerdictArgs a) {
+  __shared__ uint64_t red[64 * kNormW];
+  __shared__ uint64_t sum[2][kNormW];
+  __shared__ int pass[4];  // outer, inner, consistency, eval
+  const int tid = threadIdx.x;
+  const long long p = blockIdx.x;
+  for (int which = 0; which < 2; ++which) {
+    uint64_t acc[kNormW];
+    for (int i = 0; i < kNormW; ++i) acc[i] = 0;
+    for (int s = which ? kVerdictOuter : 0; s < (which ? kVerdictSegs : kVerdictOuter); ++s) {
+      const uint64_t* rows = a.norms[s] + p * a.cnt[s] * kNormW;
+      for (int r = tid; r < a.cnt[s]; r += 64) mw_add(acc, rows + (long long)r * kNormW, kNormW);
+    }
+    for (int i = 0; i < kNormW; ++i) red[tid * kNormW + i] = acc[i];
+    __syncthreads();
+    for (int s = 32; s > 0; s >>= 1) {
+      if (tid < s) mw_add(red + tid * kNormW, red + (tid + s) * kNormW, kNormW);
+      __syncthreads();
+    }
+    if (tid < kNormW) sum[which][tid] = red[tid];
+    __syncthreads();
+  }
+  const uint64_t* lhs = a.lhs + p * a.lhs_stride;
+  const uint64_t* rhs = a.rhs + p * a.rhs_stride;
+  if (tid < 2) {  // S < K^2, from the top word down
+    const NormBound& b = a.bound[tid];
+    int below = b.always > 0;
+    if (b.always == 0) {
+      for (int w = kNormW - 1; w >= 0; --w) {
+        if (sum[tid][w] != b.k2[w]) {
+          below = sum[tid][w] < b.k2[w];
+          break;
+        }
+      }
+    }
+    pass[tid] = below;
+  } else if (tid == 2) {
+    pass[2] = a.flag[p] == 0;
+  } else if (tid == 3) {
+    int eq = 1;
+    for (int i = 0; i < a.L; ++i) eq &= lhs[i] == rhs[i];
+    pass[3] = eq;
+  }
+  __syncthreads();
+  if (tid >= RG_JINDO_VERIFY_WORDS) return;
+  uint64_t w;
+  if (tid == 0) {
+    w = pass[0] & pass[1] & pass[2] & pass[3];
+  } else if (tid == 1) {
+    w = pass[0] | pass[1] << 1 | pass[2] << 2 | pass[3] << 3;
+  } else if (tid < 2 + 2 * kNormW) {
+    w = sum[(tid - 2) / kNormW][(tid - 2) % kNormW];
+  } else {
+    const int i = (tid - 2 - 2 * kNormW) % 16;
+    const uint64_t* side = tid < 2 + 2 * kNormW + 16 ? lhs : rhs;
+    w = i < a.L ? side[i] : 0;
+  }
+  a.out[p * RG_JINDO_VERIFY_WORDS + tid] = w;
+}
+
+// ------------------------------------------------------------------------------------------
 // Prover.Evaluate core (prover.go:205-324): the MulCoeffsMontgomeryThenAdd loops, with the
 // Fiat-Shamir challenges (batch, left, chals) injected by the caller.  Every loop is a
 // per-(limb, coeff) dot product, so each maps onto mac_kernel with J = 1 and the loop's own
@@ -455,20 +640,25 @@ using namespace rg;
 // nmTest < nm with nmTest = Float64(isqrt(S)) (verifyNorm :278-281), decided exactly: the test is
 // S < K^2 with K the smallest integer whose float64 is >= nm (ceil(nm) up to 2^53; above, the
 // midpoint below nm, + 1 when nm's mantissa is odd, as ties round to even).
-static bool norm_below(const uint64_t* S, double nm) {
+// K^2 of the bound nm as 2 kNormW words, for both entries: the single one compares on the host
+// (norm_below), the batch one hands the low half to verdict_kernel.  Returns 0 when the test is
+// S < K2; -1 when !(nm > 0), no sum is below; +1 when K^2 does not fit the sum's 640 bits, every
+// sum is below (K2 is then unspecified).
+static int norm_threshold(double nm, uint64_t K2[2 * kNormW]) {
   constexpr int NW = kNormW;
-  if (!(nm > 0)) return false;
-  uint64_t K[NW] = {0}, K2[2 * NW] = {0};
+  if (!(nm > 0)) return -1;
+  uint64_t K[NW] = {0};
+  memset(K2, 0, 2 * NW * sizeof(uint64_t));
   int e;
   const double fr = frexp(nm, &e);
   const uint64_t M = (uint64_t)ldexp(fr, 53);
   const int E = e - 53;
   if (E <= 0) {
     const double c = ceil(nm);
-    if (c >= 18446744073709551616.0) return true;
+    if (c >= 18446744073709551616.0) return 1;
     K[0] = (uint64_t)c;
   } else {
-    if (E / 64 >= NW) return true;
+    if (E / 64 >= NW) return 1;
     const int sub_e = (M == (1ull << 52)) ? E - 2 : E - 1;  // half the gap to the double below
     K[E / 64] = M << (E % 64);
     if (E % 64 && E / 64 + 1 < NW) K[E / 64 + 1] = M >> (64 - E % 64);
@@ -489,8 +679,15 @@ static bool norm_below(const uint64_t* S, double nm) {
     K2[a + NW] += c;
   }
   for (int w = 2 * NW - 1; w >= NW; --w)
-    if (K2[w]) return true;
-  for (int w = NW - 1; w >= 0; --w)
+    if (K2[w]) return 1;
+  return 0;
+}
+
+static bool norm_below(const uint64_t* S, double nm) {
+  uint64_t K2[2 * kNormW];
+  const int always = norm_threshold(nm, K2);
+  if (always) return always > 0;
+  for (int w = kNormW - 1; w >= 0; --w)
     if (S[w] != K2[w]) return S[w] < K2[w];
   return false;
 }
@@ -751,6 +948,248 @@ rg_status rg_jindo_verify_dev(const rg_jindo* J, size_t batch, const uint64_t* d
   }
   res->eval_ok = memcmp(res->eval_lhs, res->eval_rhs, 8 * L) == 0;
   res->ok = res->outer_ok && res->inner_ok && res->consistency_ok && res->eval_ok;
+  return RG_OK;
+}
+
+}  // extern "C"
+
+// ---- n_proofs proofs of one handle in one call -------------------------------------------------
+static rg_status jvm_invalid(const std::string& why) {
+  set_last_error("jindo verify multi: " + why);
+  return RG_ERR_INVALID;
+}
+
+// launch_mac's accumulator choice for `terms` products below qmax^2
+static bool acc_wide(const RnsPrime* P, int nl, int terms) {
+  uint64_t qmax = 0;
+  for (int l = 0; l < nl; ++l) qmax = std::max(qmax, P[l].q);
+  return 2.0 * log2((double)(qmax - 1)) + log2((double)terms + 1.0) >= 127.5;
+}
+
+static rg_status launch_pdot(PDotArgs a, const RnsPrime* P, size_t n_proofs, hipStream_t st) {
+  for (int l = 0; l < a.nl; ++l) a.P[l] = P[l];
+  const dim3 grid(grid256((long long)a.nout * a.nl * a.d), (unsigned)n_proofs);
+  if (acc_wide(P, a.nl, a.T))
+    hipLaunchKernelGGL(pdot_kernel<true>, grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(pdot_kernel<false>, grid, dim3(256), 0, st, a);
+  return check_launch("jindo verify multi dot");
+}
+
+template <int L>
+static rg_status launch_dot2_multi(const rg_jindo* J, size_t n_proofs, const uint64_t* x1, long long s_x1,
+                                   const uint64_t* y1, long long s_y1, long long n1, const uint64_t* x2,
+                                   const uint64_t* y2, long long n2, uint64_t* out, hipStream_t st) {
+  hipLaunchKernelGGL(dot2_multi_kernel<L>, dim3((unsigned)n_proofs), dim3(256), 0, st, field_params<L>(&J->field), x1,
+                     s_x1, y1, s_y1, n1, x2, y2, n2, out);
+  return check_launch("jindo verify multi eval");
+}
+
+// The scratch of rg_jindo_verify_multi_dev, offsets in words (N = n_proofs; every buffer proof-major):
+//   a_out [N][out_msis][nqo][d]  sum_j batchOut[j] com[j][i], then C_out in place
+//   b_out [N][out_msis][nqo][d]  sum_j Out[i][j] InCommit[j]
+//   lift  [N][dcmp][nq][d]       the inner commitments in ringQ
+//   a_in, b_in [N][in_msis][nq][d]  as a_out / b_out for verifyInnerCommitment (C_in in a_in)
+//   norms [N][dcmp | out_msis | rows | in_msis + mlwe | in_msis][kNormW]  five arrays, in this order
+//   dcd   [N][cols + 1][slots][L]  Decode of Partial and (unused) PartialMask
+//   bd    [N][batch][L]            Decode(batch[i])[0]; absent for batch == 1
+//   ev    [N][2][L]                both sides of verifyEval
+//   flag  [N] int, rounded up to a word
+struct JvmScratch {
+  size_t a_out, b_out, lift, a_in, b_in, norms[kVerdictSegs], dcd, bd, ev, flag, words;
+};
+static JvmScratch jvm_scratch(const rg_jindo_params& p, size_t N, size_t batch) {
+  const size_t pq = (size_t)p.nq * p.d, po = (size_t)p.nqo * p.d, L = p.field_limbs;
+  const size_t cnt[kVerdictSegs] = {(size_t)p.dcmp, (size_t)p.out_msis, (size_t)p.rows, (size_t)(p.in_msis + p.mlwe),
+                                    (size_t)p.in_msis};
+  JvmScratch s;
+  size_t at = 0;
+  auto take = [&](size_t words) {
+    const size_t here = at;
+    at += words;
+    return here;
+  };
+  s.a_out = take(N * p.out_msis * po);
+  s.b_out = take(N * p.out_msis * po);
+  s.lift = take(N * p.dcmp * pq);
+  s.a_in = take(N * p.in_msis * pq);
+  s.b_in = take(N * p.in_msis * pq);
+  for (int i = 0; i < kVerdictSegs; ++i) s.norms[i] = take(N * cnt[i] * kNormW);
+  s.dcd = take(N * (p.cols + 1) * p.slots * L);
+  s.bd = take(batch > 1 ? N * batch * L : 0);
+  s.ev = take(N * 2 * L);
+  s.flag = take((N * sizeof(int) + 7) / 8);
+  s.words = at;
+  return s;
+}
+
+extern "C" {
+
+size_t rg_jindo_verify_multi_scratch_bytes(const rg_jindo* J, size_t n_proofs, size_t batch) {
+  if (!J || n_proofs == 0 || n_proofs > RG_JINDO_VERIFY_MAX_PROOFS || batch < 1) return 0;
+  return jvm_scratch(J->p, n_proofs, batch).words * 8;
+}
+
+rg_status rg_jindo_verify_multi_dev(const rg_jindo* J, size_t n_proofs, size_t batch, const uint64_t* d_com,
+                                    const uint64_t* d_bq, const uint64_t* d_bo, const uint64_t* d_chals,
+                                    const uint64_t* d_left, const uint64_t* d_right, const uint64_t* d_y,
+                                    const uint64_t* d_pf_incom, const uint64_t* d_pf_partial, const uint64_t* d_pf_enc,
+                                    const uint64_t* d_pf_mlwe, double in_com_dcmp_two_nm, double res_two_nm,
+                                    uint64_t* d_out, void* d_scratch, void* stream) {
+  if (!J) return jvm_invalid("NULL handle");
+  if (n_proofs == 0 || n_proofs > RG_JINDO_VERIFY_MAX_PROOFS)
+    return jvm_invalid("n_proofs " + std::to_string(n_proofs) + " is not in [1, RG_JINDO_VERIFY_MAX_PROOFS]");
+  if (batch < 1) return jvm_invalid("batch < 1");
+  if (!d_com || !d_chals || !d_left || !d_right || !d_y || !d_pf_incom || !d_pf_partial || !d_pf_enc || !d_pf_mlwe)
+    return jvm_invalid("NULL input");
+  if (!d_out || !d_scratch) return jvm_invalid("NULL output or scratch");
+  if ((batch == 1) != (!d_bq && !d_bo) || !d_bq != !d_bo)
+    return jvm_invalid("d_bq and d_bo are both NULL iff batch == 1");
+  const rg_jindo_params& p = J->p;
+  const int d = p.d, nq = p.nq, nqo = p.nqo, L = p.field_limbs;
+  const long long pq = (long long)nq * d, po = (long long)nqo * d, nm = p.in_msis + p.mlwe;
+  const long long N = (long long)n_proofs, B = (long long)batch, cs = (long long)p.cols * p.slots;
+  if (batch > 0x7fffffffull) return jvm_invalid("batch out of range");
+  const JvmScratch S = jvm_scratch(p, n_proofs, batch);
+  {  // d_out and d_scratch overlap no input, nor each other
+    struct Span {
+      const void* p;
+      size_t words;
+    };
+    const Span in[] = {{d_com, (size_t)(N * B * p.out_msis * pq)}, {d_bq, (size_t)(N * B * pq)},
+                       {d_bo, (size_t)(N * B * po)},             {d_chals, (size_t)(N * p.cols * pq)},
+                       {d_left, (size_t)(N * p.rows * pq)},      {d_right, (size_t)(N * cs * L)},
+                       {d_y, (size_t)(N * B * L)},               {d_pf_incom, (size_t)(N * p.dcmp * po)},
+                       {d_pf_partial, (size_t)(N * (p.cols + 1) * pq)}, {d_pf_enc, (size_t)(N * p.rows * pq)},
+                       {d_pf_mlwe, (size_t)(N * nm * pq)}};
+    const Span outs[] = {{d_out, n_proofs * RG_JINDO_VERIFY_WORDS}, {d_scratch, S.words}};
+    auto overlap = [](const Span& a, const Span& b) {
+      const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+      return a.p && b.p && a0 < b0 + 8 * b.words && b0 < a0 + 8 * a.words;
+    };
+    if (overlap(outs[0], outs[1])) return jvm_invalid("d_scratch aliases d_out");
+    for (const Span& o : outs)
+      for (const Span& i : in)
+        if (overlap(o, i)) return jvm_invalid("d_out or d_scratch aliases an input");
+  }
+  RG_TRY(on_device(J));
+  hipStream_t st = as_stream(stream);
+  uint64_t* scr = static_cast<uint64_t*>(d_scratch);
+  uint64_t *a_out = scr + S.a_out, *b_out = scr + S.b_out, *lift = scr + S.lift, *a_in = scr + S.a_in,
+           *b_in = scr + S.b_in, *dcd = scr + S.dcd, *bd = scr + S.bd, *ev = scr + S.ev;
+  int* flag = reinterpret_cast<int*>(scr + S.flag);
+  auto nrm = [&](int seg) { return scr + S.norms[seg]; };
+  // verifyOuterCommitment (:136-161), every proof: A, B, C = A * 2^logOutCut - B in place, the norms
+  if (batch > 1) {
+    PDotArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = d, a.nl = nqo, a.T = (int)batch, a.nout = p.out_msis;
+    a.A = d_bo, a.a_proof = B * po, a.a_term = po;
+    a.B = d_com, a.b_proof = B * p.out_msis * pq, a.b_out = pq, a.b_term = (long long)p.out_msis * pq;
+    a.out = a_out;
+    RG_TRY(launch_pdot(a, J->ro, n_proofs, st));
+  } else {
+    RG_HIP(hipMemcpy2DAsync(a_out, 8 * po, d_com, 8 * pq, 8 * po, N * p.out_msis, hipMemcpyDeviceToDevice, st));
+  }
+  {
+    MacArgs m = dot_args(J->ro, nqo, d, N, p.dcmp, J->ck_out.as<uint64_t>(), d_pf_incom, p.dcmp * po, po, b_out);
+    m.J = p.out_msis;
+    RG_TRY(launch_mac(m, st));
+  }
+  RG_TRY(launch_combine(J->ro, nqo, d, p.log_out_cut, a_out, b_out, a_out, N * p.out_msis, st));
+  RG_TRY(launch_norm(J, true, d_pf_incom, N * p.dcmp, po, nrm(0), st));
+  RG_TRY(launch_norm(J, true, a_out, N * p.out_msis, po, nrm(1), st));
+  // verifyInnerCommitment (:164-200)
+  RG_TRY(launch_round(round_args(J, true, false, 0, d_pf_incom, lift, pq, nq), N * p.dcmp, st));
+  {
+    PDotArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = d, a.nl = nq, a.T = p.cols, a.nout = p.in_msis;
+    a.A = d_chals, a.a_proof = p.cols * pq, a.a_term = pq;
+    a.B = lift, a.b_proof = p.dcmp * pq, a.b_out = pq, a.b_term = p.in_msis * pq;
+    a.C = lift + (long long)p.cols * p.in_msis * pq, a.c_proof = p.dcmp * pq, a.c_out = pq;
+    a.out = a_in;
+    RG_TRY(launch_pdot(a, J->rq, n_proofs, st));
+  }
+  {
+    MacArgs m = dot_args(J->rq, nq, d, N, p.rows, J->ck_in.as<uint64_t>(), d_pf_enc, p.rows * pq, pq, b_in);
+    m.J = p.in_msis;
+    m.T2 = p.mlwe;
+    m.A2 = J->ck_mlwe.as<uint64_t>();
+    m.B2 = d_pf_mlwe;
+    m.b2_col = nm * pq;
+    m.b2_term = pq;
+    m.C = d_pf_mlwe + (long long)p.mlwe * pq;
+    m.c_col = nm * pq;
+    m.c_j = pq;
+    RG_TRY(launch_mac(m, st));
+  }
+  RG_TRY(launch_combine(J->rq, nq, d, p.log_in_cut, a_in, b_in, a_in, N * p.in_msis, st));
+  RG_TRY(launch_norm(J, false, d_pf_enc, N * p.rows, pq, nrm(2), st));
+  RG_TRY(launch_norm(J, false, d_pf_mlwe, N * nm, pq, nrm(3), st));
+  RG_TRY(launch_norm(J, false, a_in, N * p.in_msis, pq, nrm(4), st));
+  // verifyConsistency (:203-221)
+  RG_HIP(hipMemsetAsync(flag, 0, n_proofs * sizeof(int), st));
+  {
+    ConsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = d, a.nl = nq, a.rows = p.rows, a.cols = p.cols;
+    a.left = d_left, a.enc = d_pf_enc, a.chals = d_chals, a.partial = d_pf_partial;
+    a.flag = flag;
+    for (int l = 0; l < nq; ++l) a.P[l] = J->rq[l];
+    const dim3 grid(grid256(pq), (unsigned)n_proofs);
+    if (acc_wide(J->rq, nq, std::max(p.rows, p.cols)))
+      hipLaunchKernelGGL(consistency_kernel<true>, grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL(consistency_kernel<false>, grid, dim3(256), 0, st, a);
+    RG_TRY(check_launch("jindo verify multi consistency"));
+  }
+  // verifyEval (:224-259): Decode of every proof's Partial (PartialMask's row is decoded and left unread)
+  RG_TRY(decode_any(J, d_pf_partial, N * (p.cols + 1), p.slots, dcd, st));
+  if (batch > 1) RG_TRY(decode_any(J, d_bq, N * B, 1, bd, st));
+  RG_TRY(dispatch_limbs(L, [&](auto Lc) {
+    return launch_dot2_multi<Lc()>(J, n_proofs, d_right, cs, dcd, (long long)(p.cols + 1) * p.slots, cs, bd, d_y,
+                                   batch > 1 ? B : 0, ev, st);
+  }));
+  // the records
+  VerdictArgs v;
+  memset(&v, 0, sizeof(v));
+  v.L = L;
+  const int cnt[kVerdictSegs] = {p.dcmp, p.out_msis, p.rows, (int)nm, p.in_msis};
+  for (int i = 0; i < kVerdictSegs; ++i) {
+    v.norms[i] = nrm(i);
+    v.cnt[i] = cnt[i];
+  }
+  const double nms[2] = {in_com_dcmp_two_nm, res_two_nm};
+  for (int i = 0; i < 2; ++i) {
+    uint64_t K2[2 * kNormW];
+    v.bound[i].always = norm_threshold(nms[i], K2);
+    if (v.bound[i].always == 0) memcpy(v.bound[i].k2, K2, sizeof(v.bound[i].k2));
+  }
+  v.lhs = ev;
+  v.lhs_stride = 2 * L;
+  v.rhs = batch > 1 ? ev + L : d_y;  // batch == 1: yBatch = y[0] (:244-246)
+  v.rhs_stride = batch > 1 ? 2 * L : L;
+  v.flag = flag;
+  v.out = d_out;
+  hipLaunchKernelGGL(verdict_kernel, dim3((unsigned)n_proofs), dim3(64), 0, st, v);
+  return check_launch("jindo verify multi verdict");
+}
+
+rg_status rg_jindo_verify_unpack(const uint64_t* words, int field_limbs, rg_jindo_verify_result* res) {
+  if (!words || !res) return jvm_invalid("unpack: NULL record or result");
+  if (!limbs_supported(field_limbs))
+    return jvm_invalid("unpack: no field of " + std::to_string(field_limbs) + " limbs is built");
+  memset(res, 0, sizeof(*res));
+  res->ok = words[0] != 0;
+  res->outer_ok = (words[1] >> 0) & 1;
+  res->inner_ok = (words[1] >> 1) & 1;
+  res->consistency_ok = (words[1] >> 2) & 1;
+  res->eval_ok = (words[1] >> 3) & 1;
+  memcpy(res->outer_norm_sq, words + 2, 8 * kNormW);
+  memcpy(res->inner_norm_sq, words + 2 + kNormW, 8 * kNormW);
+  memcpy(res->eval_lhs, words + 2 + 2 * kNormW, 8 * (size_t)field_limbs);
+  memcpy(res->eval_rhs, words + 2 + 2 * kNormW + 16, 8 * (size_t)field_limbs);
   return RG_OK;
 }
 

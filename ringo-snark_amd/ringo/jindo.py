@@ -367,6 +367,11 @@ class VerifyResultC(ctypes.Structure):  # include/ringo.h rg_jindo_verify_result
                 ("ok", ctypes.c_int)]
 
 
+# include/ringo.h RG_JINDO_VERIFY_MAX_PROOFS, RG_JINDO_VERIFY_WORDS (tests/test_capi_jindo_verify_multi.py)
+VERIFY_MAX_PROOFS = 65535
+VERIFY_WORDS = 54
+
+
 @dataclass
 class VerifyResult:
     ok: bool
@@ -413,11 +418,66 @@ class Verifier:
                                         _addr(pf_partial, (P.cols + 1) * pq), _addr(pf_enc, P.rows * pq),
                                         _addr(pf_mlwe, nm * pq), float(P.in_com_dcmp_two_nm), float(P.res_two_nm),
                                         ctypes.byref(r), _stream(stream)))
+        return self._result(r)
+
+    def _result(self, r):
         word = lambda w: sum(int(x) << (64 * i) for i, x in enumerate(w))
-        L = P.L
+        L = self.params.L
         return VerifyResult(bool(r.ok), bool(r.outer_ok), bool(r.inner_ok), bool(r.consistency_ok), bool(r.eval_ok),
                             word(r.outer_norm_sq), word(r.inner_norm_sq), np.array(r.eval_lhs[:L], np.uint64),
                             np.array(r.eval_rhs[:L], np.uint64))
+
+    def verify_multi_scratch_bytes(self, n_proofs, batch):
+        """Bytes of scratch verify_multi_dev needs (0 for an n_proofs outside [1, VERIFY_MAX_PROOFS])."""
+        return lib().rg_jindo_verify_multi_scratch_bytes(self.h, n_proofs, batch)
+
+    def verify_multi_dev(self, n_proofs, batch, com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc,
+                         pf_mlwe, out, scratch, stream=None):
+        """verify_dev for n_proofs proofs in one asynchronous call (rg_jindo_verify_multi_dev): every
+        buffer has verify_dev's layout under a leading [n_proofs]; out [n_proofs][VERIFY_WORDS] receives
+        the records (unpack_verify_words) once the stream has run; scratch holds
+        verify_multi_scratch_bytes(n_proofs, batch) bytes."""
+        P = self.params
+        if P.res_two_nm is None or P.in_com_dcmp_two_nm is None:
+            raise RingoPanic("Parameters lack the two-norm bounds")
+        n, nm, pq = n_proofs, P.in_msis + P.mlwe, P.nq * P.d
+        check(lib().rg_jindo_verify_multi_dev(
+            self.h, n, batch, _addr(com, n * batch * P.out_msis * pq), _addr(bq, n * batch * pq),
+            _addr(bo, n * batch * P.nqo * P.d), _addr(chals, n * P.cols * pq), _addr(left, n * P.rows * pq),
+            _addr(right, n * P.cols * P.slots * P.L), _addr(y, n * batch * P.L), _addr(pf_incom, n * P.dcmp * P.nqo * P.d),
+            _addr(pf_partial, n * (P.cols + 1) * pq), _addr(pf_enc, n * P.rows * pq), _addr(pf_mlwe, n * nm * pq),
+            float(P.in_com_dcmp_two_nm), float(P.res_two_nm), _addr(out, n * VERIFY_WORDS),
+            _addr(scratch, self.verify_multi_scratch_bytes(n, batch) // 8), _stream(stream)))
+
+    def unpack_verify_words(self, words):
+        """The records of verify_multi_dev (host words [n][VERIFY_WORDS]) as verify_dev's result objects."""
+        words = np.ascontiguousarray(words, np.uint64).reshape(-1, VERIFY_WORDS)
+        out = []
+        for rec in words:
+            r = VerifyResultC()
+            check(lib().rg_jindo_verify_unpack(rec.ctypes.data, self.params.L, ctypes.byref(r)))
+            out.append(self._result(r))
+        return out
+
+    def VerifyMulti(self, batch, com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe):
+        """Host arrays in the verify_multi_dev layouts (the leading dimension is the proof): staged to
+        the device, one verify_multi_dev, one synchronisation, the unpacked results."""
+        import torch
+        n = len(com)
+        if n == 0:
+            return []
+        for a in (chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe) + (() if bq is None else (bq, bo)):
+            if len(a) != n:
+                raise RingoPanic("the proofs' arrays differ in length")
+        if any(len(c) != batch for c in com) or any(len(v) != batch for v in y):  # verifier.go:51-54
+            raise RingoPanic("len(v) != params.batch")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).to(dev)
+        args = [t(a) for a in (com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe)]
+        out = torch.empty((n, VERIFY_WORDS), dtype=torch.int64, device=dev)
+        scratch = torch.empty(self.verify_multi_scratch_bytes(n, batch) // 8, dtype=torch.int64, device=dev)
+        self.verify_multi_dev(n, batch, *args, out, scratch)
+        return self.unpack_verify_words(out.cpu().numpy().view(np.uint64))
 
     def Verify(self, batch, com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe):
         """Host arrays (numpy) in the verify_dev layouts: staged to the device, then verify_dev."""
