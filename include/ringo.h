@@ -750,6 +750,48 @@ rg_status rg_jindo_verify_multi_dev(const rg_jindo* j, size_t n_proofs, size_t b
                                     const uint64_t* d_pf_enc, const uint64_t* d_pf_mlwe, double in_com_dcmp_two_nm,
                                     double res_two_nm, uint64_t* d_out, void* d_scratch, void* stream);
 rg_status rg_jindo_verify_unpack(const uint64_t* words, int field_limbs, rg_jindo_verify_result* res);
+/* rg_jindo_eval_point_dev for n_points points in one enqueue: what a batch verification derives from
+ * its proofs' evaluation points, in the layouts rg_jindo_verify_multi_dev takes.
+ *   d_x     point k is the Montgomery element at d_x + k * x_stride * L words; x_stride = 5 reads the
+ *           points in place from the Buckler batch's d_chal [n_proofs][5][L] (evalPoint is element 0)
+ *   d_left  [n_points][rows][nq][d]     d_right [n_points][cols*slots][L]; NULL: not written
+ * Each point gives, word for word, what rg_jindo_eval_point_dev gives for it, left[rows-1] = x
+ * written last included (also when rows == 1).  Any shape rg_jindo_create accepts, any built limb
+ * count.
+ *
+ * Asynchronous on `stream`: nothing is allocated, freed, copied to the host or waited for inside; the
+ * handle is only read (no per-stream state, no lock), so calls on different streams with different
+ * d_scratch are independent; two launches whatever n_points (every point's leftVec and rightVec by
+ * square and multiply, a lane per element; then the encoding, a workgroup per row and point).
+ * d_scratch holds rg_jindo_eval_point_multi_scratch_bytes(j, n_points) bytes, every point's leftVec
+ * [n_points][rows][L] (0 for a NULL handle, n_points of 0 or above RG_JINDO_POINT_MAX_POINTS -- a
+ * point per grid row).  n_points == 0 returns RG_OK and touches nothing.  RG_ERR_INVALID, with the reason in rg_last_error
+ * and before the device is touched: a NULL handle, d_x, d_left or d_scratch; x_stride of 0 or above
+ * 2^30; n_points above the limit; d_left, d_right or d_scratch overlapping each other or the strided
+ * extent of d_x. */
+#define RG_JINDO_POINT_MAX_POINTS 65535
+size_t rg_jindo_eval_point_multi_scratch_bytes(const rg_jindo* j, size_t n_points);
+rg_status rg_jindo_eval_point_multi_dev(const rg_jindo* j, size_t n_points, const uint64_t* d_x, size_t x_stride,
+                                        uint64_t* d_left, uint64_t* d_right, void* d_scratch, void* stream);
+/* The whole front end of rg_jindo_verify_multi_dev, from the bytes of n_proofs replayed transcripts:
+ * the three encodeChallengeTo passes of rg_jindo_encode_challenges_dev (batch[i] into ringQ and
+ * ringQOut, chals into ringQ), then the point pass above, queued on `stream` with a launch count
+ * (5, or 3 when batch == 1) that does not depend on n_proofs.
+ *   d_x, x_stride  as above, a point per proof
+ *   d_batch_bytes  [n_proofs][batch][16]; NULL iff batch == 1     d_chal_bytes [n_proofs][cols][16]
+ *   d_bq, d_bo     [n_proofs][batch][nq | nqo][d]; both NULL iff batch == 1
+ *   d_chals [n_proofs][cols][nq][d]   d_left, d_right, d_scratch  as above
+ * The outputs are the d_bq, d_bo, d_chals, d_left and d_right arguments of rg_jindo_verify_multi_dev;
+ * a batch verification is: upload the bytes, this call, rg_buckler_verify_checks_multi_dev,
+ * rg_jindo_verify_multi_dev, on one stream.  Asynchrony, scratch (the same size:
+ * rg_jindo_verify_inputs_multi_scratch_bytes) and refusals as above, over every output and input; also
+ * refused: batch < 1 or above 32768, the NULL rule of d_batch_bytes / d_bq / d_bo, a NULL d_chal_bytes
+ * or d_chals, and a ChallengeBound of 0 (rg_jindo_challenge_bound: exp > 120). */
+size_t rg_jindo_verify_inputs_multi_scratch_bytes(const rg_jindo* j, size_t n_proofs);
+rg_status rg_jindo_verify_inputs_multi_dev(const rg_jindo* j, size_t n_proofs, size_t batch, const uint64_t* d_x,
+                                           size_t x_stride, const uint8_t* d_batch_bytes, const uint8_t* d_chal_bytes,
+                                           uint64_t* d_bq, uint64_t* d_bo, uint64_t* d_chals, uint64_t* d_left,
+                                           uint64_t* d_right, void* d_scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Device memory helpers (so a cgo caller needs no HIP headers)                           */

@@ -5,7 +5,8 @@
 // cross-GPU sum of partial openBatches.
 // The inputs of both that depend on the transcript alone are built here too: leftVec / rightVec of
 // the evaluation point with Encoder.encode of each left element (rg_jindo_eval_point_dev) and
-// encodeChallengeTo of the challenge bytes (rg_jindo_encode_challenges_dev).
+// encodeChallengeTo of the challenge bytes (rg_jindo_encode_challenges_dev); for a batch of proofs,
+// all of them in one call (rg_jindo_eval_point_multi_dev, rg_jindo_verify_inputs_multi_dev).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -630,6 +631,163 @@ static rg_status launch_encode_left(const rg_jindo* J, const uint64_t* lp, const
   a.out = out;
   hipLaunchKernelGGL(encode_left_kernel<L>, dim3((unsigned)p.rows), dim3(256), (size_t)p.nq * p.d * 8, st, a);
   return check_launch("jindo encode left");
+}
+
+// ------------------------------------------------------------------------------------------
+// The evaluation points of a batch of proofs (rg_jindo_eval_point_multi_dev): encode_left_kernel's
+// work on a (rows, point) grid, point blockIdx.y at x + blockIdx.y * x_stride words.
+//   point_powers_kernel       lane per element: leftVec[j] = x^(j cols slots) for j < rows - 1 by square and
+//                             multiply (at most 2 log2(rank) dependent products, every lane busy), x itself
+//                             for row rows - 1, and kRightPer successive powers of rightVec per further
+//                             lane.  Montgomery products are fully reduced, so the words are those of the
+//                             single entry's running-product tables.
+//   encode_left_multi_kernel  encode_left_kernel with the element read from that table
+// Measured against the single entry's two power tables per point (rg_buckler_powers_batch_dev twice
+// and a strided copy: four stream items, each table 2 (log2 + 16) products deep) and against raising
+// x in the encoding workgroups' one busy lane: profiles/jverify_inputs_timing.txt,
+// tools/experiments/jindo_point_pow_arms.patch.
+// ------------------------------------------------------------------------------------------
+constexpr int kRightPer = 4;
+
+// p = c^e
+template <int L>
+__device__ __forceinline__ void f_pow(uint64_t* p, const uint64_t* c, unsigned long long e, const uint64_t* one,
+                                      const FieldParams<L>& F) {
+  uint64_t sq[L];
+  el_copy<L>(p, one);
+  el_copy<L>(sq, c);
+  for (; e; e >>= 1) {
+    if (e & 1) f_mul<L>(p, p, sq, F);
+    if (e > 1) f_mul<L>(sq, sq, sq, F);
+  }
+}
+
+template <int L>
+struct PointPowArgs {
+  int rows;
+  long long cs;        // cols * slots: rightVec's length, and skip = x^cs
+  FieldParams<L> F;
+  Elem<L> one;         // Montgomery 1
+  const uint64_t* x;   // point k at x + k * x_stride
+  long long x_stride;  // in words
+  uint64_t* lp;        // [point][rows][L] leftVec
+  uint64_t* right;     // [point][cs][L] rightVec, or nullptr: not written
+};
+
+template <int L>
+__global__ __launch_bounds__(256) void point_powers_kernel(PointPowArgs<L> a) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x, pt = blockIdx.y;
+  uint64_t cv[L], p[L];
+  el_copy<L>(cv, a.x + pt * a.x_stride);
+  if (t < a.rows) {  // leftVec (utils.go:63-72); left[rows - 1] = x is written last, also when rows == 1
+    if (t == a.rows - 1)
+      el_copy<L>(p, cv);
+    else
+      f_pow<L>(p, cv, (unsigned long long)t * (unsigned long long)a.cs, a.one.v, a.F);
+    el_copy<L>(a.lp + (pt * a.rows + t) * L, p);
+    return;
+  }
+  // rightVec (utils.go:75-82): right[i] = x^i
+  const long long e0 = (t - a.rows) * kRightPer;
+  if (!a.right || e0 >= a.cs) return;
+  f_pow<L>(p, cv, (unsigned long long)e0, a.one.v, a.F);
+  const long long e1 = min(a.cs, e0 + kRightPer);
+  uint64_t* right = a.right + pt * a.cs * L;
+  for (long long e = e0; e < e1; ++e) {
+    el_copy<L>(right + e * L, p);
+    if (e + 1 < e1) f_mul<L>(p, p, cv, a.F);
+  }
+}
+
+// workgroup (row, point) of PointArgs with lp [point][rows][L] and out [point][rows][R.n][d]; a.x is unused
+template <int L>
+__global__ __launch_bounds__(256) void encode_left_multi_kernel(PointArgs<L> a) {
+  extern __shared__ uint64_t poly_lds[];
+  const int d = a.d, tid = threadIdx.x, nl = a.R.n;
+  const long long el = (long long)blockIdx.y * a.rows + blockIdx.x;
+  for (int k = tid; k < nl * d; k += blockDim.x) poly_lds[k] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t xv[L], c[L];
+    el_copy<L>(xv, a.lp + el * L);
+    f_redc<L>(c, xv, a.F);  // Slice = fromMont
+    auto put = [&](int j, uint32_t dg) {  // MForm(digit) at coefficient j * slots (digit < 2^32 <= any word)
+      for (int l = 0; l < nl; ++l) {
+        const RnsPrime& P = a.R.p[l];
+        poly_lds[(long long)l * d + j * a.slots] = sh_mul(dg, P.r64, P.r64_sh, P.q);
+      }
+    };
+    bool done = false;
+    if constexpr (L == 4 || L == 2) {
+      if (a.dc.exp == a.exp) {
+        dc_digits<L>(c, a.dc, put);
+        done = true;
+      }
+    }
+    if (!done) {  // exp - 1 remainders, then the last quotient (encoder.go:125-136)
+      uint32_t w[2 * L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        w[2 * l] = (uint32_t)c[l];
+        w[2 * l + 1] = (uint32_t)(c[l] >> 32);
+      }
+      for (int jd = 0; jd < a.exp - 1; ++jd) {
+        uint64_t rem = 0;
+        for (int k = 2 * L - 1; k >= 0; --k) w[k] = divstep((rem << 32) | w[k], a.base, a.base_inv, rem);
+        put(jd, (uint32_t)rem);
+      }
+      put(a.exp - 1, w[0]);
+    }
+  }
+  __syncthreads();
+  ntt_store(poly_lds, a.R, d, a.out + el * nl * d);
+}
+
+// The scratch of rg_jindo_eval_point_multi_dev in words: leftVec of every point, [N][rows][L]
+static size_t point_multi_words(const rg_jindo_params& p, size_t N) {
+  return N * (size_t)p.rows * p.field_limbs;
+}
+
+// the point pass of both batch entries, arguments checked by the caller: two launches
+template <int L>
+static rg_status point_multi_L(const rg_jindo* J, size_t N, const uint64_t* x, size_t x_stride, uint64_t* left,
+                               uint64_t* right, uint64_t* lp, hipStream_t st) {
+  const rg_jindo_params& p = J->p;
+  PointPowArgs<L> w;
+  memset(&w, 0, sizeof(w));
+  w.rows = p.rows;
+  w.cs = (long long)p.cols * p.slots;
+  w.F = field_params<L>(&J->field);
+  w.one = elem<L>(J->field.one);
+  w.x = x;
+  w.x_stride = (long long)(x_stride * L);
+  w.lp = lp;
+  w.right = right;
+  const long long lanes = p.rows + (right ? (w.cs + kRightPer - 1) / kRightPer : 0);
+  hipLaunchKernelGGL(point_powers_kernel<L>, dim3(grid256(lanes), (unsigned)N), dim3(256), 0, st, w);
+  RG_TRY(check_launch("jindo point powers"));
+  PointArgs<L> a;
+  memset(&a, 0, sizeof(a));
+  a.d = p.d;
+  a.slots = p.slots;
+  a.exp = p.exp;
+  a.rows = p.rows;
+  a.R = ring_dev(J->rq, p.nq, J->rootsq_f, J->rootsq_b);
+  a.F = w.F;
+  a.base = p.base;
+  a.base_inv = J->base_inv;
+  a.dc = dc_constants((uint64_t)p.base, p.exp, L, field_bits(J->field));
+  a.lp = lp;
+  a.out = left;
+  hipLaunchKernelGGL(encode_left_multi_kernel<L>, dim3((unsigned)p.rows, (unsigned)N), dim3(256),
+                     (size_t)p.nq * p.d * 8, st, a);
+  return check_launch("jindo encode left multi");
+}
+
+static rg_status point_multi(const rg_jindo* J, size_t N, const uint64_t* x, size_t x_stride, uint64_t* left,
+                             uint64_t* right, uint64_t* scratch, hipStream_t st) {
+  return dispatch_limbs(J->p.field_limbs,
+                        [&](auto Lc) { return point_multi_L<Lc()>(J, N, x, x_stride, left, right, scratch, st); });
 }
 
 }  // namespace rg
@@ -1262,6 +1420,130 @@ rg_status rg_jindo_encode_challenges_dev(const rg_jindo* J, int ring, const uint
   a.out = d_out;
   hipLaunchKernelGGL(encode_chal_kernel, dim3((unsigned)n), dim3(256), (size_t)a.R.n * p.d * 8, as_stream(stream), a);
   return check_launch("jindo encode challenges");
+}
+
+}  // extern "C"
+
+// ---- the inputs of a batch verification: every proof's point and challenges in one call -------
+namespace {
+
+struct Span {
+  const char* name;
+  const void* p;
+  size_t bytes;
+};
+
+bool spans_overlap(const Span& a, const Span& b) {
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a.p && b.p && a.bytes && b.bytes && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+// no output overlaps another output or an input; the reason names the pair
+rg_status check_disjoint(const char* who, const Span* outs, size_t n_out, const Span* ins, size_t n_in) {
+  for (size_t i = 0; i < n_out; ++i) {
+    for (size_t k = 0; k < i; ++k)
+      if (spans_overlap(outs[i], outs[k])) {
+        set_last_error(std::string(who) + ": " + outs[i].name + " overlaps " + outs[k].name);
+        return RG_ERR_INVALID;
+      }
+    for (size_t k = 0; k < n_in; ++k)
+      if (spans_overlap(outs[i], ins[k])) {
+        set_last_error(std::string(who) + ": " + outs[i].name + " overlaps " + ins[k].name);
+        return RG_ERR_INVALID;
+      }
+  }
+  return RG_OK;
+}
+
+constexpr size_t kPointMaxStride = (size_t)1 << 30;  // rg_buckler_powers_batch_dev's limit on a base stride
+
+// what both entries ask of the points; n > 0
+rg_status check_points(const char* who, size_t n, const uint64_t* d_x, size_t x_stride) {
+  auto invalid = [&](const std::string& why) {
+    set_last_error(std::string(who) + ": " + why);
+    return RG_ERR_INVALID;
+  };
+  if (n > RG_JINDO_POINT_MAX_POINTS)
+    return invalid(std::to_string(n) + " points: at most RG_JINDO_POINT_MAX_POINTS, a point per grid row");
+  if (!d_x) return invalid("NULL d_x");
+  if (x_stride == 0 || x_stride > kPointMaxStride) return invalid("x_stride is not in [1, 2^30]");
+  return RG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rg_jindo_eval_point_multi_scratch_bytes(const rg_jindo* J, size_t n_points) {
+  if (!J || n_points == 0 || n_points > RG_JINDO_POINT_MAX_POINTS) return 0;
+  return point_multi_words(J->p, n_points) * 8;
+}
+
+rg_status rg_jindo_eval_point_multi_dev(const rg_jindo* J, size_t n_points, const uint64_t* d_x, size_t x_stride,
+                                        uint64_t* d_left, uint64_t* d_right, void* d_scratch, void* stream) {
+  static const char who[] = "jindo eval point multi";
+  if (!J) {
+    set_last_error(std::string(who) + ": NULL handle");
+    return RG_ERR_INVALID;
+  }
+  if (n_points == 0) return RG_OK;
+  RG_TRY(check_points(who, n_points, d_x, x_stride));
+  if (!d_left || !d_scratch) {
+    set_last_error(std::string(who) + ": NULL d_left or d_scratch");
+    return RG_ERR_INVALID;
+  }
+  const rg_jindo_params& p = J->p;
+  const size_t N = n_points, L = p.field_limbs, pq = (size_t)p.nq * p.d;
+  const Span outs[] = {{"d_left", d_left, N * p.rows * pq * 8},
+                       {"d_right", d_right, N * p.cols * p.slots * L * 8},
+                       {"d_scratch", d_scratch, point_multi_words(p, N) * 8}};
+  const Span ins[] = {{"the points of d_x", d_x, ((N - 1) * x_stride + 1) * L * 8}};
+  RG_TRY(check_disjoint(who, outs, 3, ins, 1));
+  RG_TRY(on_device(J));
+  return point_multi(J, N, d_x, x_stride, d_left, d_right, static_cast<uint64_t*>(d_scratch), as_stream(stream));
+}
+
+size_t rg_jindo_verify_inputs_multi_scratch_bytes(const rg_jindo* J, size_t n_proofs) {
+  return rg_jindo_eval_point_multi_scratch_bytes(J, n_proofs);
+}
+
+rg_status rg_jindo_verify_inputs_multi_dev(const rg_jindo* J, size_t n_proofs, size_t batch, const uint64_t* d_x,
+                                           size_t x_stride, const uint8_t* d_batch_bytes, const uint8_t* d_chal_bytes,
+                                           uint64_t* d_bq, uint64_t* d_bo, uint64_t* d_chals, uint64_t* d_left,
+                                           uint64_t* d_right, void* d_scratch, void* stream) {
+  static const char who[] = "jindo verify inputs multi";
+  auto invalid = [&](const std::string& why) {
+    set_last_error(std::string(who) + ": " + why);
+    return RG_ERR_INVALID;
+  };
+  if (!J) return invalid("NULL handle");
+  if (n_proofs == 0) return RG_OK;
+  RG_TRY(check_points(who, n_proofs, d_x, x_stride));
+  if (batch < 1 || batch > 0x7fffffffull / RG_JINDO_POINT_MAX_POINTS) return invalid("batch out of range");
+  if (!d_chal_bytes || !d_chals || !d_left || !d_scratch) return invalid("NULL d_chal_bytes, d_chals, d_left or d_scratch");
+  if ((batch == 1) != (!d_batch_bytes && !d_bq && !d_bo) || !d_bq != !d_bo || !d_bq != !d_batch_bytes)
+    return invalid("d_batch_bytes, d_bq and d_bo are all NULL iff batch == 1");
+  const rg_jindo_params& p = J->p;
+  uint64_t bound = 0;
+  RG_TRY(rg_jindo_challenge_bound(&p, &bound));
+  const size_t N = n_proofs, L = p.field_limbs, pq = (size_t)p.nq * p.d, po = (size_t)p.nqo * p.d;
+  const Span outs[] = {{"d_bq", d_bq, N * batch * pq * 8},
+                       {"d_bo", d_bo, N * batch * po * 8},
+                       {"d_chals", d_chals, N * p.cols * pq * 8},
+                       {"d_left", d_left, N * p.rows * pq * 8},
+                       {"d_right", d_right, N * p.cols * p.slots * L * 8},
+                       {"d_scratch", d_scratch, point_multi_words(p, N) * 8}};
+  const Span ins[] = {{"the points of d_x", d_x, ((N - 1) * x_stride + 1) * L * 8},
+                      {"d_batch_bytes", d_batch_bytes, N * batch * 16},
+                      {"d_chal_bytes", d_chal_bytes, N * p.cols * 16}};
+  RG_TRY(check_disjoint(who, outs, 6, ins, 3));
+  RG_TRY(on_device(J));
+  if (batch > 1) {  // batch[i] in ringQ and batchOut[i] in ringQOut (verifier.go:74-80)
+    RG_TRY(rg_jindo_encode_challenges_dev(J, 0, d_batch_bytes, N * batch, d_bq, stream));
+    RG_TRY(rg_jindo_encode_challenges_dev(J, 1, d_batch_bytes, N * batch, d_bo, stream));
+  }
+  RG_TRY(rg_jindo_encode_challenges_dev(J, 0, d_chal_bytes, N * p.cols, d_chals, stream));
+  return point_multi(J, N, d_x, x_stride, d_left, d_right, static_cast<uint64_t*>(d_scratch), as_stream(stream));
 }
 
 rg_status rg_jindo_eval_reduce_dev(const rg_jindo* J, uint64_t* d_ob_incom, uint64_t* d_ob_enc, uint64_t* d_ob_mlwe,

@@ -198,6 +198,11 @@ _SIGS = {
     "rg_jindo_verify_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t] + [vp] * 11 +
                                   [ctypes.c_double, ctypes.c_double, vp, vp, vp]),
     "rg_jindo_verify_unpack": (ctypes.c_int, [vp, ctypes.c_int, vp]),
+    "rg_jindo_eval_point_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_jindo_eval_point_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, vp, vp]),
+    "rg_jindo_verify_inputs_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_jindo_verify_inputs_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t] +
+                                         [vp] * 9),
     "rg_malloc": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_size_t]),
     "rg_free": (ctypes.c_int, [vp]),
     "rg_memcpy_h2d": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp]),

@@ -328,6 +328,20 @@ class Prover:
         check(lib().rg_jindo_eval_point_dev(self.h, _addr(x, P.L), _addr(left, P.rows * P.nq * P.d),
                                             _addr(right, P.cols * P.slots * P.L), _stream(stream)))
 
+    def eval_point_multi_scratch_bytes(self, n_points):
+        """Bytes of scratch eval_point_multi_dev needs (0 for an n_points outside [1, POINT_MAX_POINTS])."""
+        return lib().rg_jindo_eval_point_multi_scratch_bytes(self.h, n_points)
+
+    def eval_point_multi_dev(self, n_points, x, x_stride, left, right, scratch, stream=None):
+        """eval_point_dev for n_points points in one asynchronous call (rg_jindo_eval_point_multi_dev):
+        point k is the element at x + k * x_stride * L words, left [n_points][rows][nq][d], right
+        [n_points][cols*slots][L] or None; scratch holds eval_point_multi_scratch_bytes(n_points) bytes."""
+        P, n = self.params, n_points
+        check(lib().rg_jindo_eval_point_multi_dev(
+            self.h, n, _addr(x, ((n - 1) * x_stride + 1) * P.L if n else None), x_stride,
+            _addr(left, n * P.rows * P.nq * P.d), _addr(right, n * P.cols * P.slots * P.L),
+            _addr(scratch, self.eval_point_multi_scratch_bytes(n) // 8), _stream(stream)))
+
     def encode_challenges_dev(self, ring, bytes, n, out, stream=None):
         """encodeChallengeTo (utils.go:20-46) of n challenges: bytes, a device buffer of n * 16 bytes
         (a uint8 tensor or an int address), into out [n][nq or nqo][d] of ringQ (ring 0) or
@@ -370,6 +384,8 @@ class VerifyResultC(ctypes.Structure):  # include/ringo.h rg_jindo_verify_result
 # include/ringo.h RG_JINDO_VERIFY_MAX_PROOFS, RG_JINDO_VERIFY_WORDS (tests/test_capi_jindo_verify_multi.py)
 VERIFY_MAX_PROOFS = 65535
 VERIFY_WORDS = 54
+# include/ringo.h RG_JINDO_POINT_MAX_POINTS (tests/test_capi_jindo_verify_inputs.py)
+POINT_MAX_POINTS = 65535
 
 
 @dataclass
@@ -401,6 +417,33 @@ class Verifier:
     def encode_challenges_dev(self, ring, bytes, n, out, stream=None):
         """encodeChallengeTo of n challenges on the device (Prover.encode_challenges_dev)."""
         self._p.encode_challenges_dev(ring, bytes, n, out, stream)
+
+    def eval_point_multi_scratch_bytes(self, n_points):
+        """Bytes of scratch eval_point_multi_dev needs (Prover.eval_point_multi_scratch_bytes)."""
+        return self._p.eval_point_multi_scratch_bytes(n_points)
+
+    def eval_point_multi_dev(self, n_points, x, x_stride, left, right, scratch, stream=None):
+        """encode(leftVec(x)) and rightVec(x) of n_points points in one call (Prover.eval_point_multi_dev)."""
+        self._p.eval_point_multi_dev(n_points, x, x_stride, left, right, scratch, stream)
+
+    def verify_inputs_multi_scratch_bytes(self, n_proofs):
+        """Bytes of scratch verify_inputs_multi_dev needs (0 for an n_proofs outside [1, POINT_MAX_POINTS])."""
+        return lib().rg_jindo_verify_inputs_multi_scratch_bytes(self.h, n_proofs)
+
+    def verify_inputs_multi_dev(self, n_proofs, batch, x, x_stride, batch_bytes, chal_bytes, bq, bo, chals, left,
+                                right, scratch, stream=None):
+        """Everything verify_multi_dev reads besides the proofs, from the transcripts' bytes, in one
+        asynchronous call (rg_jindo_verify_inputs_multi_dev): x and x_stride as eval_point_multi_dev,
+        batch_bytes [n_proofs][batch][16] and chal_bytes [n_proofs][cols][16] uint8 device buffers, into
+        bq, bo, chals, left, right in verify_multi_dev's layouts; batch_bytes = bq = bo = None iff
+        batch == 1; scratch holds verify_inputs_multi_scratch_bytes(n_proofs) bytes."""
+        P, n, pq = self.params, n_proofs, self.params.nq * self.params.d
+        check(lib().rg_jindo_verify_inputs_multi_dev(
+            self.h, n, batch, _addr(x, ((n - 1) * x_stride + 1) * P.L if n else None), x_stride,
+            _byte_addr(batch_bytes, n * batch * 16), _byte_addr(chal_bytes, n * P.cols * 16),
+            _addr(bq, n * batch * pq), _addr(bo, n * batch * P.nqo * P.d), _addr(chals, n * P.cols * pq),
+            _addr(left, n * P.rows * pq), _addr(right, n * P.cols * P.slots * P.L),
+            _addr(scratch, self.verify_inputs_multi_scratch_bytes(n) // 8), _stream(stream)))
 
     def verify_dev(self, batch, com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe,
                    stream=None):
