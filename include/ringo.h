@@ -428,6 +428,74 @@ rg_status rg_buckler_verify_checks_multi(const rg_bverifier* v, size_t n_proofs,
                                          const uint64_t* mask_sums, uint64_t* verdict, uint64_t* sides,
                                          uint64_t* pw_evals);
 
+/* ---- Buckler prover's checks for a batch of proofs (buckler/prover.go:399-485) ------------- */
+/* Prover.arithCheck, linCheck and sumCheck of n_proofs proofs of one compiled circuit, enqueued by
+ * one call whose launch count does not depend on n_proofs: the prover's counterpart of
+ * rg_buckler_verify_checks_multi_dev, with its vocabulary, layouts and limits.  All four challenges
+ * are fixed before arithCheck runs (prover.go:242-334), so one call does the whole round and leaves,
+ * for every proof, the seven polynomials Prove commits next; each output, being proof-major, goes
+ * straight into rg_jindo_commit_dev with batch = n_proofs.  Everything is Montgomery, canonical and
+ * injected; the transcript, the masks (rg_buckler_sumcheck_mask_dev, one round earlier) and the
+ * commits stay with the caller.
+ *
+ * The handle holds what Compile fixes.  enc_plan / emb_plan: the encoder's cyclic plan at the witness
+ * rank and the evaluator's cyclic plan at the embedding rank (a negacyclic plan is RG_ERR_INVALID).
+ * lin / arith / sum: HasLinearCheck / HasArithmeticCheck / HasSumCheck; each may be NULL, all three
+ * NULL is RG_ERR_INVALID.  arith_max_rank / sum_max_rank: ctx.arithCheckMaxRank / sumCheckMaxRank,
+ * read for a present check only.  Handles are borrowed and outlive the prover.  RG_ERR_INVALID also
+ * for: a `lin` whose plans differ in rank or field from enc_plan / emb_plan, a circuit of another
+ * field, a circuit or pair index >= n_w, a public-witness index >= n_pw, jindo_rank < rank - 1 (or
+ * above 2^32), a present check with max_rank < rank or max_rank > the embedding rank.
+ * RG_ERR_UNSUPPORTED for a limb count other than 1, 2, 4, 7, 14.  rg_last_error has the reason.
+ * Creating a prover touches no device.
+ *
+ * Every array is proof-major.  Inputs: d_w [n_proofs][n_w][emb][L] = wEcdNTT (NULL iff n_w = 0);
+ * d_pw [n_proofs][n_pw][emb][L] = pwEcdNTT (NULL iff n_pw = 0); d_xof [n_proofs][32 * rank] bytes,
+ * each proof's projection matrix (prover.go:165-176), required iff `lin` holds a projection checker
+ * and NULL otherwise -- the checkers' own matrices are neither read nor changed; d_chal
+ * [n_proofs][4][L]: arithBatchConst, linCheckBatchConst, linCheckConst, sumCheckBatchConst; d_lin_mask,
+ * d_sum_mask [n_proofs][emb][L] (linCheckMask, sumCheckMask).  Outputs, with n_quo = arith_max_rank -
+ * rank, rank, sum_max_rank - rank for arith, lin, sum: quo [n_proofs][n_quo][L]; remLo
+ * [n_proofs][rank-1][L]; remHi [n_proofs][jindo_rank][L] = jindo_rank - (rank-1) zeros, then remLo
+ * (arithCheck discards its remainder).  Optional d_rem0 [n_proofs][2][L]: element 0 of linCheck's
+ * and of sumCheck's remPoly, the sums the verifier compares with LinCheckMaskSum / SumCheckMaskSum
+ * (verifier.go:288-293; the single entry leaves lin's at rg_buckler_lin_check_rem_offset_bytes);
+ * zeros for an absent check.  The pointers of an absent check must be NULL; a quo with n_quo = 0 may
+ * be NULL and nothing is written.
+ *
+ * The pipeline: one rg_buckler_powers_batch_dev of every proof's linCheckConst, each checker's
+ * transpose over all proofs in one call (rg_buckler_checker_transpose_xof_dev for a projection
+ * checker), ONE batched Encode and ONE batched NTT at the embedding rank over the n_proofs * (1 +
+ * n_chk) vectors, one kernel per check for the NTT-domain evaluation (linCheck's pass and evalCircuit
+ * with a proof per grid row, the trailing ScalarMulTo of linCheck and sumCheck folded in), ONE batched
+ * InvNTT over all n_proofs * n_checks evals and ONE kernel with the mask add, QuoRemByVanishing and
+ * the quo / remLo / remHi / rem0 split of every check.  Each output word has one writer; nothing is
+ * allocated, copied back or waited for inside.
+ *
+ * n_proofs = 0 does nothing.  RG_ERR_INVALID for n_proofs > RG_BK_MULTI_MAX_PROOFS, for n_proofs *
+ * max(1 + n_chk, n_checks) > 2^30 polynomials or more than 2^39 words in them, and for any two
+ * aliased buffers; every argument is validated before the device is touched.  d_scratch holds
+ * rg_buckler_prove_checks_scratch_bytes(p, n_proofs) bytes (0 for an n_proofs that is refused); calls
+ * on different streams use different scratch.  The form without `_dev` takes host pointers and is
+ * synchronous. */
+typedef struct rg_bprover rg_bprover;
+rg_status rg_buckler_prover_create(const rg_ntt* enc_plan, const rg_ntt* emb_plan, size_t jindo_rank, size_t n_w,
+                                   size_t n_pw, const rg_lincheck* lin, const rg_circuit* arith, size_t arith_max_rank,
+                                   const rg_circuit* sum, size_t sum_max_rank, rg_bprover** out);
+void rg_buckler_prover_destroy(rg_bprover* p);
+size_t rg_buckler_prove_checks_scratch_bytes(const rg_bprover* p, size_t n_proofs);
+rg_status rg_buckler_prove_checks_dev(const rg_bprover* p, size_t n_proofs, const uint64_t* d_w, const uint64_t* d_pw,
+                                      const uint8_t* d_xof, const uint64_t* d_chal, const uint64_t* d_lin_mask,
+                                      const uint64_t* d_sum_mask, uint64_t* d_arith_quo, uint64_t* d_lin_quo,
+                                      uint64_t* d_lin_rem_lo, uint64_t* d_lin_rem_hi, uint64_t* d_sum_quo,
+                                      uint64_t* d_sum_rem_lo, uint64_t* d_sum_rem_hi, uint64_t* d_rem0,
+                                      uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_prove_checks(const rg_bprover* p, size_t n_proofs, const uint64_t* w, const uint64_t* pw,
+                                  const uint8_t* xof, const uint64_t* chal, const uint64_t* lin_mask,
+                                  const uint64_t* sum_mask, uint64_t* arith_quo, uint64_t* lin_quo,
+                                  uint64_t* lin_rem_lo, uint64_t* lin_rem_hi, uint64_t* sum_quo, uint64_t* sum_rem_lo,
+                                  uint64_t* sum_rem_hi, uint64_t* rem0);
+
 /* ---- Buckler norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---- */
 /* decomposeBig on the device: a Montgomery element w is taken out of Montgomery form, centred
  * (x > q >> 1 stands for x - q) and walked down the base b_0, b_1, ...: digit +1 and x -= b_j while

@@ -1,8 +1,9 @@
 // buckler_impl.hpp -- what the Buckler units share: the handle definitions of the constraint
 // program (buckler.hip), the checkers and the linear check (buckler_lin.hip), and the one decode of
 // each handle's device program into pointers (circ_prog, lin_prog), read by the prover's passes and
-// by the verifier's checks (buckler_verify.hip).  Every kernel and launcher stays in its unit, and
-// the verifier reaches them through the `_dev` entries of include/ringo.h.
+// by the verifier's checks (buckler_verify.hip), and the handle of the prover's batch call
+// (buckler_prove.hip).  Every kernel and launcher stays in its unit, and the verifier and the batch
+// prover reach them through the `_dev` entries of include/ringo.h.
 #pragma once
 #include <string.h>
 
@@ -45,6 +46,21 @@ struct rg_lincheck {
   int n_pairs = 0;
   long long max_w = -1;
   rg::DevBuf prog;  // pair_off [n_chk+1] u32 | pairs [n_pairs][2] u32 (wOut, wIn)
+};
+
+// What Compile fixes for the prover's three checks (buckler_prove.hip); every handle is borrowed
+struct rg_bprover {
+  const rg_ntt* enc = nullptr;  // cyclic at the witness rank
+  const rg_ntt* emb = nullptr;  // cyclic at the embedding rank
+  const rg_lincheck* lin = nullptr;
+  const rg_circuit* arith = nullptr;
+  const rg_circuit* sum = nullptr;
+  long long rank = 0, emb_rank = 0, jindo_rank = 0;
+  size_t n_w = 0, n_pw = 0;
+  size_t n_lin_vec = 0;  // 1 + n_chk with a linear check, else 0
+  size_t n_checks = 0;   // the checks present; their evals stand in the order arith, lin, sum
+  size_t arith_n_quo = 0, sum_n_quo = 0;  // max_rank - rank (lin's is rank)
+  bool has_proj = false;
 };
 
 namespace rg {

@@ -152,6 +152,12 @@ _SIGS = {
     "rg_buckler_verify_checks_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
     "rg_buckler_verify_checks_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t] + [vp] * 10),
     "rg_buckler_verify_checks_multi": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p, ctypes.c_char_p] + [u64p] * 5),
+    "rg_buckler_prover_create": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp,
+                                                ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_buckler_prover_destroy": (None, [vp]),
+    "rg_buckler_prove_checks_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_buckler_prove_checks_dev": (ctypes.c_int, [vp, ctypes.c_size_t] + [vp] * 16),
+    "rg_buckler_prove_checks": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p, ctypes.c_char_p] + [u64p] * 11),
     "rg_buckler_dcmp_create": (ctypes.c_int, [vp, u64p, ctypes.c_size_t, ctypes.POINTER(vp)]),
     "rg_buckler_dcmp_destroy": (None, [vp]),
     "rg_buckler_dcmp_inf_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),

@@ -29,6 +29,11 @@ and the verifier's checks (buckler/verifier.go:178-315), one proof or a batch of
     plan = VerifyPlan(F, rank, jindoRank, wCnt, nPw, lin, arith, sum)
     verdict, sides, pwEvals = plan.checks(evals, pw, chal, maskSums)
     verdicts, sides, pwEvals = plan.checks_multi(evals, pw, xof, chal, maskSums)   # [n] in front of each
+
+and the prover's three checks (buckler/prover.go:399-485) for a batch of proofs of one circuit in one call:
+
+    plan = ProvePlan(F, rank, embRank, jindoRank, nW, nPw, lin, arith, arithMaxRank, sum, sumMaxRank)
+    arithQuo, linQuo, linRemLo, linRemHi, sumQuo, sumRemLo, sumRemHi, rem0 = plan.checks(w, pw, xof, chal, linMask, sumMask)
 """
 import ctypes
 
@@ -656,6 +661,114 @@ def VerifyChecks(field, rank, jindoRank, wCnt, challenges, maskSums, evals, pw, 
     if np.asarray(evals).reshape(-1, field.L).shape[0] < plan.n_evals:
         raise RingoPanic("index out of range")  # pf.Evals[roundComIdx]
     return plan.checks(np.asarray(evals, np.uint64).reshape(-1, field.L)[:plan.n_evals], pw, challenges, maskSums)
+
+
+# ---- the prover's checks for a batch of proofs (buckler/prover.go:399-485) --------------------------
+class ProvePlan:
+    """What Prover.arithCheck / linCheck / sumCheck take from the compiled context (rg_bprover): the
+    encoder's plan at `rank`, the evaluator's at `embRank`, jindoRank, the numbers of witnesses and
+    public witnesses, and the linear check (a LinCheckPlan), the arithmetic and the sum-check
+    constraints (Circuit objects or constraint lists) with ctx.arithCheckMaxRank / sumCheckMaxRank,
+    each check optional."""
+
+    def __init__(self, field, rank, embRank, jindoRank, nW, nPw, lin=None, arith=None, arithMaxRank=0, sum=None,
+                 sumMaxRank=0, enc=None, emb=None):
+        self.field, self.rank, self.embRank, self.jindoRank, self.nW, self.nPw = field, rank, embRank, jindoRank, nW, nPw
+        self.enc = enc if enc is not None else (lin.enc if lin is not None else NewCyclicTransformer(field, rank))
+        self.emb = emb if emb is not None else (lin.emb if lin is not None else NewCyclicTransformer(field, embRank))
+        as_circ = lambda c: c if c is None or isinstance(c, Circuit) else Circuit(field, c)  # noqa: E731
+        self.lin, self.arith, self.sum = lin, as_circ(arith), as_circ(sum)  # kept alive: the handle borrows them
+        self.hasProj = lin is not None and any(isinstance(c, ProjChecker) for c in lin.checkers)
+        # elements per proof of the eight outputs, in the order of the C call (None: the check is absent)
+        self.nQuo = (arithMaxRank - rank if self.arith is not None else None, rank if lin is not None else None,
+                     sumMaxRank - rank if self.sum is not None else None)
+        h = vp()
+        _status(lib().rg_buckler_prover_create(
+            self.enc.h, self.emb.h, jindoRank, nW, nPw, lin.h if lin is not None else None,
+            self.arith.h if self.arith is not None else None, arithMaxRank,
+            self.sum.h if self.sum is not None else None, sumMaxRank, ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_buckler_prover_destroy(self.h)
+            self.h = None
+
+    def scratch_bytes(self, n_proofs):
+        return lib().rg_buckler_prove_checks_scratch_bytes(self.h, n_proofs)
+
+    def out_elems(self):
+        """Elements per proof of (arithQuo, linQuo, linRemLo, linRemHi, sumQuo, sumRemLo, sumRemHi, rem0);
+        None for the outputs of an absent check."""
+        a, l, s = self.nQuo
+        lo, hi = self.rank - 1, self.jindoRank
+        return (a, l, None if l is None else lo, None if l is None else hi, s, None if s is None else lo,
+                None if s is None else hi, 2)
+
+    def checks_dev(self, n_proofs, d_w, d_pw, d_xof, d_chal, d_lin_mask, d_sum_mask, d_arith_quo, d_lin_quo,
+                   d_lin_rem_lo, d_lin_rem_hi, d_sum_quo, d_sum_rem_lo, d_sum_rem_hi, d_rem0=None, d_scratch=None,
+                   stream=None):
+        """rg_buckler_prove_checks_dev: every buffer proof-major.  d_w [n][nW][embRank][L], d_pw
+        [n][nPw][embRank][L] (None iff nPw = 0), d_xof [n][rank * 32] uint8 (None iff the linear check has
+        no projection checker), d_chal [n][4][L] (arithBatchConst, linCheckBatchConst, linCheckConst,
+        sumCheckBatchConst), the masks [n][embRank][L]; outputs quo [n][n_quo][L], remLo [n][rank-1][L],
+        remHi [n][jindoRank][L], optional d_rem0 [n][2][L].  The buffers of an absent check are None.
+        Asynchronous on `stream`."""
+        L, n, emb = self.field.L, n_proofs, self.embRank
+        opt = lambda t, w: _addr(t, w) if t is not None else None  # noqa: E731
+        outs = (d_arith_quo, d_lin_quo, d_lin_rem_lo, d_lin_rem_hi, d_sum_quo, d_sum_rem_lo, d_sum_rem_hi, d_rem0)
+        _status(lib().rg_buckler_prove_checks_dev(
+            self.h, n, opt(d_w, n * self.nW * emb * L), opt(d_pw, n * self.nPw * emb * L),
+            _xof_addr(d_xof, n * self.rank * 32), _addr(d_chal, n * 4 * L), opt(d_lin_mask, n * emb * L),
+            opt(d_sum_mask, n * emb * L), *[opt(t, n * (k or 0) * L) for t, k in zip(outs, self.out_elems())],
+            opt(d_scratch, self.scratch_bytes(n) // 8), _stream(stream)))
+
+    def checks(self, w, pw, xof, chal, linMask, sumMask):
+        """rg_buckler_prove_checks (host arrays, synchronous): w [n][nW][embRank][L], pw
+        [n][nPw][embRank][L] (None iff nPw = 0), xof n * rank * 32 bytes or None, chal [n][4][L], the masks
+        [n][embRank][L] (None for an absent check) -> (arithQuo, linQuo, linRemLo, linRemHi, sumQuo,
+        sumRemLo, sumRemHi, rem0), each [n][.][L], None for an absent check."""
+        L, emb = self.field.L, self.embRank
+        ch = np.ascontiguousarray(np.asarray(chal, np.uint64).reshape(-1, 4, L))
+        n = ch.shape[0]
+        arr = lambda a, *s: None if a is None else np.ascontiguousarray(np.asarray(a, np.uint64).reshape(n, *s, L))  # noqa: E731
+        wa = None if self.nW == 0 else arr(w, self.nW, emb)
+        pwa = None if self.nPw == 0 else arr(pw, self.nPw, emb)
+        if xof is not None:
+            xof = bytes(xof)
+            if len(xof) < n * self.rank * 32:
+                raise RingoPanic("index out of range")
+        outs = [None if k is None else np.full((max(n, 1), max(k, 1), L), 2 ** 64 - 1, np.uint64)
+                for k in self.out_elems()]
+        _status(lib().rg_buckler_prove_checks(self.h, n, ptr(wa), ptr(pwa), xof, ptr(ch), ptr(arr(linMask, emb)),
+                                              ptr(arr(sumMask, emb)), *[ptr(o) for o in outs]))
+        return tuple(None if o is None else o[:n, :k] for o, k in zip(outs, self.out_elems()))
+
+
+def ProveChecks(field, rank, embRank, jindoRank, challenges, linCheckMasks, sumCheckMasks, checkers, linConstraints,
+                arithConstraints, arithCheckMaxRank, sumConstraints, sumCheckMaxRank, wEcdNTT, pwEcdNTT, xof=None):
+    """Prover.arithCheck, linCheck and sumCheck (prover.go:399-485) of a batch of proofs of one
+    circuit.  challenges [n][4][L] = arithBatchConst, linCheckBatchConst, linCheckConst,
+    sumCheckBatchConst per proof; linCheckMasks / sumCheckMasks [n][embRank][L]; wEcdNTT
+    [n][nW][embRank][L] and pwEcdNTT [n][nPw][embRank][L] (None without any); xof = the n proofs'
+    projection bytes, rank * 32 each (None without a projection checker).  A check whose constraints
+    are None is absent.  Returns one tuple per proof: (arithQuo, (linQuo, linRemLo, linRemHi),
+    (sumQuo, sumRemLo, sumRemHi), (linRem0, sumRem0)), None in place of an absent check."""
+    lin = None
+    if linConstraints is not None:
+        lin = linConstraints if isinstance(linConstraints, LinCheckPlan) else LinCheckPlan(field, rank, embRank,
+                                                                                           checkers, linConstraints)
+    w = None if wEcdNTT is None else np.asarray(wEcdNTT, np.uint64)
+    pw = None if pwEcdNTT is None else np.asarray(pwEcdNTT, np.uint64)
+    nW = 0 if w is None else w.shape[1]
+    nPw = 0 if pw is None else pw.shape[1]
+    plan = ProvePlan(field, rank, embRank, jindoRank, nW, nPw, lin, arithConstraints, arithCheckMaxRank,
+                     sumConstraints, sumCheckMaxRank)
+    aq, lq, llo, lhi, sq, slo, shi, rem0 = plan.checks(w, pw, xof, challenges, linCheckMasks if lin is not None else None,
+                                                       sumCheckMasks if plan.sum is not None else None)
+    return [(None if aq is None else aq[i], None if lq is None else (lq[i], llo[i], lhi[i]),
+             None if sq is None else (sq[i], slo[i], shi[i]), (rem0[i, 0], rem0[i, 1])) for i in range(rem0.shape[0])]
 
 
 # ---- norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---------------
