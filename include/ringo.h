@@ -537,6 +537,64 @@ rg_status rg_buckler_dcmp_proj(const rg_dcmp* h, const uint64_t* w, size_t rank,
 rg_status rg_buckler_dcmp_two(const rg_dcmp* h, const uint64_t* w, size_t batch, size_t rank, uint64_t* out,
                               uint64_t* sq);
 
+/* ---- Buckler prover's projection round and masks for a batch of proofs (prover.go:165-240) ---- */
+/* What Prove does between two batched commit rounds, for n_proofs proofs of one compiled circuit and
+ * in the vocabulary of rg_buckler_prove_checks_dev: every array proof-major, Montgomery and canonical,
+ * every argument validated before the device is touched (rg_last_error has the reason), everything
+ * asynchronous on `stream`, nothing allocated, copied back or waited for inside (one exception below),
+ * every output word written by exactly one writer, a launch count without n_proofs in it.  n_proofs =
+ * 0 does nothing; n_proofs > RG_BK_MULTI_MAX_PROOFS and any two aliased buffers are RG_ERR_INVALID; a
+ * limb count other than 1, 2, 4, 7, 14 is RG_ERR_UNSUPPORTED.  The XOF, the transcript, SetBytes and
+ * decomposeBase stay with the caller.
+ *
+ * The projection round (prover.go:165-193).  The handle holds what Compile fixes: the field, the
+ * witness rank, the number of witnesses n_w of the table and the n_c approximate infinity-norm
+ * constraints, cons [n_c][3] = the witness IDs (src, proj, dcmp) of each, with dcmp[c] the borrowed
+ * rg_dcmp of decomposeBase(rank * bound) of constraint c (context.go:206-228); the bases may differ in
+ * length.  Creating it touches no device.  RG_ERR_INVALID for rank < 128 (or above 2^30), n_c = 0 or
+ * n_c > 32 (the constraint table travels as kernel arguments), an index >= n_w, 128 nb > rank for any
+ * constraint, an rg_dcmp of another field, and an output row (proj or dcmp) that is another output row
+ * or any constraint's src: the reference ranges over a map there, so no order is defined that a result
+ * could depend on.  Several constraints may share one src.
+ *
+ * d_w [n_proofs][n_w][rank][L]: the plain witness table as wData.w holds it, read and written in
+ * place.  d_xof [n_proofs][32 * rank] bytes: each proof's projection matrix (prover.go:168-176), the
+ * bytes rg_buckler_prove_checks_dev takes later; entry (i, j) is true iff bit i % 8 of byte i / 8 of
+ * column j's 32 bytes is 0.  For every proof and constraint, row proj becomes TransformTo(w[src])
+ * under the proof's matrix (the 128 sums in entries 0 .. 127, zeros above, linear.go:108-123) and row
+ * dcmp becomes out[i nb + j] = digit j of proj[i] for i < 128, zeros from 128 nb (prover.go:182-192),
+ * the digits as rg_buckler_dcmp_proj_dev writes them.  Every other row of d_w is left untouched.
+ *
+ * Two launches: one with the matrix products of all proofs and constraints, a workgroup per 512
+ * columns that reads its XOF bytes straight into LDS (no pack launch, no bit-matrix scratch, no
+ * checker handle) and leaves one partial row; one that sums the partial rows in column order,
+ * decomposes and stores both rows with their zero tails.  No atomics.  d_scratch holds
+ * rg_buckler_prove_proj_round_scratch_bytes(h, n_proofs) = n_proofs * n_c * ceil(rank / 512) * 128 * L * 8
+ * bytes (0 for an n_proofs that is refused); calls on different streams use different scratch and may
+ * share the handle.  The bases reach the device by the rg_dcmp handles' own first-use rule: the first
+ * call that uses a handle nobody has used yet uploads its base and waits for that copy (capture a
+ * graph only after it).  The form without `_dev` takes host pointers and is synchronous. */
+typedef struct rg_bproj rg_bproj;
+rg_status rg_buckler_proj_round_create(const rg_field* f, size_t rank, size_t n_w, size_t n_c, const uint64_t* cons,
+                                       const rg_dcmp* const* dcmp, rg_bproj** out);
+void rg_buckler_proj_round_destroy(rg_bproj* h);
+size_t rg_buckler_prove_proj_round_scratch_bytes(const rg_bproj* h, size_t n_proofs);
+rg_status rg_buckler_prove_proj_round_dev(const rg_bproj* h, size_t n_proofs, uint64_t* d_w, const uint8_t* d_xof,
+                                          uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_prove_proj_round(const rg_bproj* h, size_t n_proofs, uint64_t* w, const uint8_t* xof);
+/* Prover.sumCheckMask(maskRank) (prover.go:381-397) of n_proofs proofs in one launch, with the
+ * constraints and refusals of rg_buckler_sumcheck_mask_dev.  d_rand [n_proofs][mask_rank][L]: the draws
+ * in the reference's order.  d_mask [n_proofs][emb_rank][L]: what rg_buckler_prove_checks_dev takes as
+ * d_lin_mask / d_sum_mask.  d_mask_com (optional) [n_proofs][mask_rank][L]: mask.Coeffs[:maskRank] of
+ * every proof, contiguous, as rg_jindo_commit_dev takes it with batch = n_proofs and nv = mask_rank.
+ * d_mask_sum [n_proofs][L].  The call needs no scratch. */
+rg_status rg_buckler_sumcheck_mask_batch_dev(const rg_field* f, size_t rank, size_t mask_rank, size_t emb_rank,
+                                             size_t n_proofs, const uint64_t* d_rand, uint64_t* d_mask,
+                                             uint64_t* d_mask_com, uint64_t* d_mask_sum, void* stream);
+rg_status rg_buckler_sumcheck_mask_batch(const rg_field* f, size_t rank, size_t mask_rank, size_t emb_rank,
+                                         size_t n_proofs, const uint64_t* rand, uint64_t* mask, uint64_t* mask_com,
+                                         uint64_t* mask_sum);
+
 /* ------------------------------------------------------------------------------------ */
 /* Jindo commitment (jindo/params.go, encoder.go, rns.go, prover.go, entities.go)         */
 /* ------------------------------------------------------------------------------------ */

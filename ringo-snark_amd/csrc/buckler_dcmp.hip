@@ -14,6 +14,7 @@
 #include <mutex>
 #include <vector>
 
+#include "buckler_impl.hpp"
 #include "common.hpp"
 #include "dcmp.hpp"
 #include "field.hpp"
@@ -259,6 +260,15 @@ static bool proj_args_ok(const rg_dcmp* h, const void* w, size_t rank, const voi
 }
 static bool two_args_ok(const rg_dcmp* h, const void* w, size_t batch, size_t rank, const void* out) {
   return h && w && out && out != w && rank >= 1 && rank <= kMaxRank && batch <= kMaxBatch && (size_t)h->nb <= rank;
+}
+
+// the handle as the projection round reads it (buckler_impl.hpp)
+DcmpView dcmp_view(const rg_dcmp* h) { return DcmpView{&h->f, h->nb, h->one, h->neg_one}; }
+
+rg_status dcmp_base_dev(const rg_dcmp* h, const uint64_t** d_base) {
+  RG_TRY(ensure_base(h));
+  *d_base = h->base.as<uint64_t>();
+  return RG_OK;
 }
 
 }  // namespace rg

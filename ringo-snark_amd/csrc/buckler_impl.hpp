@@ -105,4 +105,16 @@ inline LinProg lin_prog(const rg_lincheck* lc) {
   return p;
 }
 
+// What the projection round (buckler_proj.hip) reads of a decomposition handle, whose definition
+// stays in buckler_dcmp.hip.  dcmp_view touches no device; dcmp_base_dev gives the base's device
+// copy [nb][L] under the handle's first-use rule (the first caller uploads it and waits for the copy).
+struct DcmpView {
+  const rg_field* f;
+  long long nb;
+  const uint64_t* one;      // SetInt64(1)
+  const uint64_t* neg_one;  // SetInt64(-1)
+};
+DcmpView dcmp_view(const rg_dcmp* h);
+rg_status dcmp_base_dev(const rg_dcmp* h, const uint64_t** d_base);
+
 }  // namespace rg

@@ -34,6 +34,12 @@ and the prover's three checks (buckler/prover.go:399-485) for a batch of proofs 
 
     plan = ProvePlan(F, rank, embRank, jindoRank, nW, nPw, lin, arith, arithMaxRank, sum, sumMaxRank)
     arithQuo, linQuo, linRemLo, linRemHi, sumQuo, sumRemLo, sumRemHi, rem0 = plan.checks(w, pw, xof, chal, linMask, sumMask)
+
+and what stands between the commit rounds before them (buckler/prover.go:165-240), for the same batch:
+
+    proj = ProjRoundPlan(F, rank, nW, [(src, projID, dcmpID, Decomposer(F, rank * bound))])
+    w = proj.round(w, xof)                                     # the proj and dcmp rows of every proof
+    masks, maskComs, maskSums = SumCheckMaskBatch(F, rank, maskRank, embRank, rand)
 """
 import ctypes
 
@@ -769,6 +775,81 @@ def ProveChecks(field, rank, embRank, jindoRank, challenges, linCheckMasks, sumC
                                                        sumCheckMasks if plan.sum is not None else None)
     return [(None if aq is None else aq[i], None if lq is None else (lq[i], llo[i], lhi[i]),
              None if sq is None else (sq[i], slo[i], shi[i]), (rem0[i, 0], rem0[i, 1])) for i in range(rem0.shape[0])]
+
+
+# ---- the projection round and the masks for a batch of proofs (buckler/prover.go:165-240) ------------
+class ProjRoundPlan:
+    """What the projection round (prover.go:165-193) takes from the compiled context (rg_bproj): the
+    witness rank, the number of witnesses nW of the table, and the approximate infinity-norm
+    constraints as (src, proj, dcmp, decomposer) tuples: three witness IDs and the Decomposer of
+    decomposeBase(rank * bound), or the bound itself (an int)."""
+
+    def __init__(self, field, rank, nW, constraints):
+        self.field, self.rank, self.nW = field, rank, nW
+        self.constraints = [(int(s), int(p), int(d), dc if isinstance(dc, Decomposer) else Decomposer(field, rank * dc))
+                            for s, p, d, dc in constraints]  # the decomposers kept alive: the handle borrows them
+        flat = [i for c in self.constraints for i in c[:3]]
+        cons = (ctypes.c_uint64 * max(1, len(flat)))(*flat)
+        hs = (vp * max(1, len(self.constraints)))(*[c[3].h.value for c in self.constraints])
+        h = vp()
+        _status(lib().rg_buckler_proj_round_create(field.h, rank, nW, len(self.constraints), cons, hs, ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_buckler_proj_round_destroy(self.h)
+            self.h = None
+
+    def scratch_bytes(self, n_proofs):
+        return lib().rg_buckler_prove_proj_round_scratch_bytes(self.h, n_proofs)
+
+    def round_dev(self, n_proofs, d_w, d_xof, d_scratch=None, stream=None):
+        """rg_buckler_prove_proj_round_dev: d_w [n][nW][rank][L], the plain witness table, whose proj and
+        dcmp rows are written in place; d_xof [n][rank * 32] uint8.  Asynchronous on `stream`."""
+        n = n_proofs
+        _status(lib().rg_buckler_prove_proj_round_dev(
+            self.h, n, _addr(d_w, n * self.nW * self.rank * self.field.L), _xof_addr(d_xof, n * self.rank * 32),
+            _addr(d_scratch, self.scratch_bytes(n) // 8) if d_scratch is not None else None, _stream(stream)))
+
+    def round(self, w, xof):
+        """rg_buckler_prove_proj_round (host arrays, synchronous): w [n][nW][rank][L], xof n * rank * 32
+        bytes -> the table with the proj and dcmp rows of every proof filled in (a copy)."""
+        w = np.array(np.asarray(w, np.uint64).reshape(-1, self.nW, self.rank, self.field.L), order="C")
+        n = w.shape[0]
+        xof = bytes(xof)
+        if len(xof) < n * self.rank * 32:
+            raise RingoPanic("index out of range")
+        _status(lib().rg_buckler_prove_proj_round(self.h, n, ptr(w), xof))
+        return w
+
+
+def SumCheckMaskBatch(field, rank, maskRank, embRank, rand):
+    """Prover.sumCheckMask(maskRank) (prover.go:381-397) of a batch of proofs; rand [n][maskRank][L] =
+    each proof's MustSetRandom draws in the reference's order.  Returns (mask [n][embRank][L], maskCom
+    [n][maskRank][L] = mask.Coeffs[:maskRank], maskSum [n][L])."""
+    L = field.L
+    if maskRank > embRank:
+        raise RingoPanic("index out of range")
+    r = np.ascontiguousarray(np.asarray(rand, np.uint64).reshape(-1, maskRank, L))
+    n = r.shape[0]
+    mask = np.zeros((max(n, 1), embRank, L), np.uint64)
+    com = np.zeros((max(n, 1), maskRank, L), np.uint64)
+    msum = np.zeros((max(n, 1), L), np.uint64)
+    _status(lib().rg_buckler_sumcheck_mask_batch(field.h, rank, maskRank, embRank, n, ptr(r), ptr(mask), ptr(com),
+                                                 ptr(msum)))
+    return mask[:n], com[:n], msum[:n]
+
+
+def sumcheck_mask_batch_dev(field, rank, maskRank, embRank, n_proofs, d_rand, d_mask, d_mask_sum, d_mask_com=None,
+                            stream=None):
+    """rg_buckler_sumcheck_mask_batch_dev: d_rand [n][maskRank][L] -> d_mask [n][embRank][L], d_mask_sum
+    [n][L] and, when given, d_mask_com [n][maskRank][L]."""
+    L, n = field.L, n_proofs
+    _status(lib().rg_buckler_sumcheck_mask_batch_dev(
+        field.h, rank, maskRank, embRank, n, _addr(d_rand, n * maskRank * L), _addr(d_mask, n * embRank * L),
+        _addr(d_mask_com, n * maskRank * L) if d_mask_com is not None else None, _addr(d_mask_sum, n * L),
+        _stream(stream)))
 
 
 # ---- norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---------------
