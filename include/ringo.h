@@ -919,6 +919,66 @@ rg_status rg_jindo_verify_inputs_multi_dev(const rg_jindo* j, size_t n_proofs, s
                                            uint64_t* d_bq, uint64_t* d_bo, uint64_t* d_chals, uint64_t* d_left,
                                            uint64_t* d_right, void* d_scratch, void* stream);
 
+/* Prover.Evaluate (prover.go:205-324) for n_proofs proofs of one handle, in two enqueues around the
+ * caller's transcript, which Evaluate reads twice: the batch bytes before openBatch, the challenge
+ * bytes after Partial / PartialMask have been absorbed.  A batch is: upload the points and batch
+ * bytes, call 1, download d_pf_partial, absorb and squeeze on the host, upload the challenge bytes,
+ * call 2 (and rg_poly_evaluate_multi_dev for the evaluations), all on one stream.
+ *
+ * 1. rg_jindo_eval_open_multi_dev (:227-289): the batch challenges' encodings, encode(leftVec(x)),
+ *    openBatch and the partials of every proof.
+ *      d_incom, d_enc, d_mlwe  the openings: opening t of proof p starts p * open_proof_stride +
+ *          t * open_commit_stride openings in, one opening being one [dcmp][nqo][d],
+ *          [cols+1][rows][nq][d] or [cols+1][in_msis+mlwe][nq][d] block of the respective array.
+ *          Strides (batch, 1) read a [proof][commit] buffer; (1, n_proofs) read the [commit][proof]
+ *          buffers that one rg_jindo_commit_dev per round with batch = n_proofs leaves behind.
+ *      d_x, x_stride   as rg_jindo_eval_point_multi_dev, a point per proof, read in place
+ *      d_batch_bytes   [n_proofs][batch][16]
+ *      d_ob_enc  [n_proofs][cols+1][rows][nq][d]   d_ob_mlwe [n_proofs][cols+1][in_msis+mlwe][nq][d]
+ *      d_pf_incom   [n_proofs][dcmp][nqo][d]  openBatch.InCommit = Proof.InCommit
+ *      d_pf_partial [n_proofs][cols+1][nq][d]  Partial, then PartialMask
+ *    batch == 1: openBatch = open[0] (:267-269); d_batch_bytes, d_ob_enc and d_ob_mlwe are all NULL
+ *    (with batch > 1 none of them is), d_pf_incom receives a copy of each proof's InCommit, the
+ *    partials come straight from d_enc, and the caller hands d_enc and d_mlwe themselves to call 2
+ *    with ob_proof_stride = open_proof_stride.
+ *    Stream items: 7 for batch > 1 (two challenge encodings, two for the point pass, the InCommit and
+ *    MLWE combinations, and one kernel that forms openBatch.Encode and the partials together: every
+ *    opening word of Encode read once, openBatch.Encode written once and never read back), 4 for
+ *    batch == 1 (the point pass, the InCommit copy, the partials).
+ * 2. rg_jindo_eval_respond_multi_dev (:296-316): the response challenges' encodings, Proof.Encode and
+ *    Proof.MLWE of every proof.
+ *      d_ob_enc, d_ob_mlwe  the openBatch of proof p starts p * ob_proof_stride openings in: 1 after
+ *                           call 1, open_proof_stride when batch == 1 and the openings are passed
+ *      d_chal_bytes [n_proofs][cols][16]
+ *      d_pf_enc [n_proofs][rows][nq][d]   d_pf_mlwe [n_proofs][in_msis+mlwe][nq][d]
+ *    Stream items: 3 (the encoding, the two response products), whatever batch was.
+ * Every output word is the canonical residue the single entries (rg_jindo_encode_challenges_dev,
+ * rg_jindo_eval_point_dev, rg_jindo_eval_batch_dev, rg_jindo_eval_partial_dev,
+ * rg_jindo_eval_respond_dev) give for that proof.
+ *
+ * Both are asynchronous on `stream`: nothing is allocated, freed, copied to the host or waited for
+ * inside, the handle is only read, and the counts above do not depend on n_proofs.  d_scratch holds
+ * rg_jindo_eval_open_multi_scratch_bytes(j, n_proofs, batch) resp.
+ * rg_jindo_eval_respond_multi_scratch_bytes(j, n_proofs) bytes; both return 0 for the arguments the
+ * call refuses (a NULL handle, n_proofs of 0 or above RG_JINDO_EVAL_MAX_PROOFS -- a proof per grid
+ * row --, batch < 1 or above 32768).  RG_ERR_INVALID, with a reason in rg_last_error that starts
+ * "jindo eval multi" and before the device is touched: a NULL handle, required buffer or scratch;
+ * n_proofs or batch out of range; a stride of 0 (or above 2^31; x_stride above 2^30); the NULL rule
+ * broken either way; a ChallengeBound of 0 (rg_jindo_challenge_bound); an output or the scratch
+ * overlapping an input or another output, the extent of a strided input being its last opening's end. */
+#define RG_JINDO_EVAL_MAX_PROOFS 65535
+size_t rg_jindo_eval_open_multi_scratch_bytes(const rg_jindo* j, size_t n_proofs, size_t batch);
+rg_status rg_jindo_eval_open_multi_dev(const rg_jindo* j, size_t n_proofs, size_t batch, const uint64_t* d_incom,
+                                       const uint64_t* d_enc, const uint64_t* d_mlwe, size_t open_proof_stride,
+                                       size_t open_commit_stride, const uint64_t* d_x, size_t x_stride,
+                                       const uint8_t* d_batch_bytes, uint64_t* d_ob_enc, uint64_t* d_ob_mlwe,
+                                       uint64_t* d_pf_incom, uint64_t* d_pf_partial, void* d_scratch, void* stream);
+size_t rg_jindo_eval_respond_multi_scratch_bytes(const rg_jindo* j, size_t n_proofs);
+rg_status rg_jindo_eval_respond_multi_dev(const rg_jindo* j, size_t n_proofs, const uint64_t* d_ob_enc,
+                                          const uint64_t* d_ob_mlwe, size_t ob_proof_stride,
+                                          const uint8_t* d_chal_bytes, uint64_t* d_pf_enc, uint64_t* d_pf_mlwe,
+                                          void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Device memory helpers (so a cgo caller needs no HIP headers)                           */
 /* ------------------------------------------------------------------------------------ */

@@ -1564,3 +1564,322 @@ rg_status rg_jindo_eval_reduce_dev(const rg_jindo* J, uint64_t* d_ob_incom, uint
 }
 
 }  // extern "C"
+
+// ---- Prover.Evaluate for n_proofs proofs of one handle, in two calls around the transcript ----
+// rg_jindo_eval_open_multi_dev (prover.go:227-289) and rg_jindo_eval_respond_multi_dev (:296-316).
+// The challenge encodings and the point pass are the kernels above with n = n_proofs * batch (or
+// cols) and a point per proof; the InCommit and MLWE combinations and the response products are
+// pdot_kernel with the proof stride on both operands.  What is new is
+//   eval_open_kernel  workgroup per (proof, column i, tile of 64 limb * coeff positions), its waves (4, or
+//                     16 from kEvalManyRows rows on: one proof alone has only (cols + 1) * tiles workgroups)
+//                     splitting the rows j as dot_split_kernel splits its terms.  Per row a wave forms
+//                     openBatch.Encode[i][j] = sum_t batch[t] * open[t].Encode[i][j] exactly, reduces it,
+//                     stores it and multiplies it by left[j] into a second exact accumulator, so
+//                     Partial[i] = sum_j left[j] * openBatch.Encode[i][j] never reads openBatch.Encode
+//                     back; the waves' sums are added through LDS and reduced once.  The proof's
+//                     batch-challenge tile sits in LDS up to kEvalLdsBatch commits (16 KB) and is read
+//                     from global memory (L2) above.  WB / WR: the third accumulator word for the sum
+//                     over the batch / over the rows, each by launch_mac's criterion.
+//   gather_kernel     batch == 1: Proof.InCommit = open[0].InCommit of every proof, a strided copy
+namespace rg {
+
+constexpr int kEvalLdsBatch = 32;
+constexpr int kEvalManyRows = 32;  // from here on 16 waves split the rows, below 4
+
+struct EvalOpenArgs {
+  int d, nl, rows, cols, batch;
+  const uint64_t* enc;               // opening t of proof p at p * enc_proof + t * enc_commit words
+  long long enc_proof, enc_commit;
+  const uint64_t* bq;                // [proof][batch][nl][d]
+  const uint64_t* left;              // [proof][rows][nl][d]
+  uint64_t* ob_enc;                  // [proof][cols + 1][rows][nl][d]
+  uint64_t* partial;                 // [proof][cols + 1][nl][d]
+  RnsPrime P[kMaxQ];
+};
+
+// dynamic LDS: the batch-challenge tile [batch][64] (LDSB), then the waves' sums [waves - 1][3][64]
+template <bool WB, bool WR, bool LDSB>
+__global__ __launch_bounds__(1024) void eval_open_kernel(EvalOpenArgs a) {
+  extern __shared__ uint64_t eval_lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  uint64_t(*bt)[64] = reinterpret_cast<uint64_t(*)[64]>(eval_lds);
+  uint64_t(*red)[3][64] = reinterpret_cast<uint64_t(*)[3][64]>(eval_lds + (LDSB ? a.batch * 64 : 0));
+  const long long per_col = (long long)a.nl * a.d;
+  const unsigned ntile = (unsigned)((per_col + 63) / 64);
+  const long long lk = (long long)(blockIdx.x % ntile) * 64 + lane;
+  const long long col = blockIdx.x / ntile, p = blockIdx.y;
+  const bool ok = lk < per_col;  // nl * d need not be a multiple of 64 (d = 8)
+  const uint64_t* bq = a.bq + p * a.batch * per_col + lk;
+  if constexpr (LDSB) {
+    for (int t = w; t < a.batch; t += nw) bt[t][lane] = ok ? bq[t * per_col] : 0;
+    __syncthreads();
+  }
+  Acc<WR> part;
+  part.zero();
+  if (ok) {
+    const RnsPrime& P = a.P[(int)(lk / a.d)];
+    const uint64_t* e0 = a.enc + p * a.enc_proof + col * a.rows * per_col + lk;
+    const uint64_t* left = a.left + p * a.rows * per_col + lk;
+    uint64_t* ob = a.ob_enc + (p * (a.cols + 1) + col) * a.rows * per_col + lk;
+    for (int j = w; j < a.rows; j += nw) {
+      const uint64_t* e = e0 + j * per_col;
+      const uint64_t lv = left[j * per_col];
+      Acc<WB> s;
+      s.zero();
+#pragma unroll 4
+      for (int t = 0; t < a.batch; ++t) {
+        uint64_t b;
+        if constexpr (LDSB)
+          b = bt[t][lane];
+        else
+          b = bq[t * per_col];
+        s.mac(b, e[t * a.enc_commit]);
+      }
+      const uint64_t v = s.reduce(P);
+      ob[j * per_col] = v;
+      part.mac(lv, v);
+    }
+  }
+  if (w > 0) {
+    red[w - 1][0][lane] = part.lo;
+    red[w - 1][1][lane] = part.hi;
+    red[w - 1][2][lane] = part.top;
+  }
+  __syncthreads();
+  if (w != 0 || !ok) return;
+  for (int v = 0; v < nw - 1; ++v) {  // exact: the whole sum over the rows fits the width chosen for it
+    uint32_t c1 = 0;
+    part.lo = addc(part.lo, red[v][0][lane], c1);
+    if constexpr (WR) {
+      uint32_t c2 = 0, c3 = 0;
+      part.hi = addc(part.hi, red[v][1][lane], c2);
+      part.hi = addc(part.hi, (uint64_t)c1, c3);
+      part.top += (uint32_t)red[v][2][lane] + c2 + c3;
+    } else {
+      part.hi += red[v][1][lane] + c1;
+    }
+  }
+  a.partial[(p * (a.cols + 1) + col) * per_col + lk] = part.reduce(a.P[(int)(lk / a.d)]);
+}
+
+// out [proof][words] = in[proof * in_stride ..]; blockIdx.y is the proof
+__global__ __launch_bounds__(256) void gather_kernel(const uint64_t* in, long long in_stride, uint64_t* out,
+                                                     long long words) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < words) out[blockIdx.y * words + i] = in[blockIdx.y * in_stride + i];
+}
+
+static rg_status launch_eval_open(const EvalOpenArgs& a, size_t n_proofs, hipStream_t st) {
+  const bool wb = acc_wide(a.P, a.nl, a.batch), wr = acc_wide(a.P, a.nl, a.rows), lds = a.batch <= kEvalLdsBatch;
+  const unsigned ntile = (unsigned)(((long long)a.nl * a.d + 63) / 64);
+  const dim3 grid(ntile * (unsigned)(a.cols + 1), (unsigned)n_proofs);
+  const int nw = a.rows >= kEvalManyRows ? 16 : 4;
+  const size_t shmem = ((lds ? (size_t)a.batch * 64 : 0) + (size_t)(nw - 1) * 3 * 64) * 8;
+  auto go = [&](auto WB, auto WR, auto LDSB) {
+    hipLaunchKernelGGL((eval_open_kernel<WB(), WR(), LDSB()>), grid, dim3(64 * nw), shmem, st, a);
+  };
+  auto pick_lds = [&](auto WB, auto WR) {
+    if (lds)
+      go(WB, WR, std::true_type{});
+    else
+      go(WB, WR, std::false_type{});
+  };
+  auto pick_wr = [&](auto WB) {
+    if (wr)
+      pick_lds(WB, std::true_type{});
+    else
+      pick_lds(WB, std::false_type{});
+  };
+  if (wb)
+    pick_wr(std::true_type{});
+  else
+    pick_wr(std::false_type{});
+  return check_launch("jindo eval multi open");
+}
+
+// The scratch of rg_jindo_eval_open_multi_dev in words (N = n_proofs): bq [N][batch][nq][d] and bo
+// [N][batch][nqo][d] (absent for batch == 1), left [N][rows][nq][d], then the point pass's own
+struct JemScratch {
+  size_t bq, bo, left, lp, words;
+};
+static JemScratch jem_scratch(const rg_jindo_params& p, size_t N, size_t batch) {
+  const size_t pq = (size_t)p.nq * p.d, po = (size_t)p.nqo * p.d;
+  JemScratch s;
+  s.bq = 0;
+  s.bo = s.bq + (batch > 1 ? N * batch * pq : 0);
+  s.left = s.bo + (batch > 1 ? N * batch * po : 0);
+  s.lp = s.left + N * p.rows * pq;
+  s.words = s.lp + point_multi_words(p, N);
+  return s;
+}
+
+constexpr size_t kEvalMaxBatch = 0x7fffffffull / RG_JINDO_EVAL_MAX_PROOFS;  // n_proofs * batch encodings in one grid
+constexpr size_t kEvalMaxStride = (size_t)1 << 31;
+
+// bytes from the first word of a strided array of `openings` openings of `words` words to its last
+// opening's end; 0 where that passes 2^62 (refused by the callers)
+static size_t strided_bytes(unsigned __int128 openings, size_t words) {
+  const unsigned __int128 b = openings * words * 8;
+  return b >> 62 ? 0 : (size_t)b;
+}
+
+}  // namespace rg
+
+extern "C" {
+
+size_t rg_jindo_eval_open_multi_scratch_bytes(const rg_jindo* J, size_t n_proofs, size_t batch) {
+  if (!J || n_proofs == 0 || n_proofs > RG_JINDO_EVAL_MAX_PROOFS || batch < 1 || batch > kEvalMaxBatch) return 0;
+  return jem_scratch(J->p, n_proofs, batch).words * 8;
+}
+
+rg_status rg_jindo_eval_open_multi_dev(const rg_jindo* J, size_t n_proofs, size_t batch, const uint64_t* d_incom,
+                                       const uint64_t* d_enc, const uint64_t* d_mlwe, size_t open_proof_stride,
+                                       size_t open_commit_stride, const uint64_t* d_x, size_t x_stride,
+                                       const uint8_t* d_batch_bytes, uint64_t* d_ob_enc, uint64_t* d_ob_mlwe,
+                                       uint64_t* d_pf_incom, uint64_t* d_pf_partial, void* d_scratch, void* stream) {
+  static const char who[] = "jindo eval multi open";
+  auto invalid = [&](const std::string& why) {
+    set_last_error(std::string(who) + ": " + why);
+    return RG_ERR_INVALID;
+  };
+  if (!J) return invalid("NULL handle");
+  if (n_proofs == 0 || n_proofs > RG_JINDO_EVAL_MAX_PROOFS)
+    return invalid("n_proofs " + std::to_string(n_proofs) + " is not in [1, RG_JINDO_EVAL_MAX_PROOFS]");
+  if (batch < 1 || batch > kEvalMaxBatch) return invalid("batch is not in [1, " + std::to_string(kEvalMaxBatch) + "]");
+  if (!d_incom || !d_enc || !d_mlwe) return invalid("NULL d_incom, d_enc or d_mlwe");
+  if (open_proof_stride == 0 || open_commit_stride == 0 || open_proof_stride > kEvalMaxStride ||
+      open_commit_stride > kEvalMaxStride)
+    return invalid("open_proof_stride and open_commit_stride are not in [1, 2^31]");
+  RG_TRY(check_points(who, n_proofs, d_x, x_stride));
+  if (!d_pf_incom || !d_pf_partial || !d_scratch) return invalid("NULL d_pf_incom, d_pf_partial or d_scratch");
+  if ((batch == 1) != (!d_batch_bytes && !d_ob_enc && !d_ob_mlwe) || !d_ob_enc != !d_ob_mlwe ||
+      !d_ob_enc != !d_batch_bytes)
+    return invalid("d_batch_bytes, d_ob_enc and d_ob_mlwe are all NULL iff batch == 1");
+  const rg_jindo_params& p = J->p;
+  uint64_t bound = 0;
+  if (rg_jindo_challenge_bound(&p, &bound) != RG_OK) return invalid("ChallengeBound() is 0 (exp > 120)");
+  const size_t N = n_proofs, L = p.field_limbs, pq = (size_t)p.nq * p.d, po = (size_t)p.nqo * p.d;
+  const size_t nm = (size_t)p.in_msis + p.mlwe, w_inc = (size_t)p.dcmp * po, w_enc = (size_t)(p.cols + 1) * p.rows * pq,
+               w_ml = (size_t)(p.cols + 1) * nm * pq;
+  const JemScratch S = jem_scratch(p, N, batch);
+  {
+    const unsigned __int128 openings =
+        (unsigned __int128)(N - 1) * open_proof_stride + (unsigned __int128)(batch - 1) * open_commit_stride + 1;
+    const Span ins[] = {{"d_incom", d_incom, strided_bytes(openings, w_inc)},
+                        {"d_enc", d_enc, strided_bytes(openings, w_enc)},
+                        {"d_mlwe", d_mlwe, strided_bytes(openings, w_ml)},
+                        {"the points of d_x", d_x, ((N - 1) * x_stride + 1) * L * 8},
+                        {"d_batch_bytes", d_batch_bytes, N * batch * 16}};
+    for (int i = 0; i < 3; ++i)
+      if (!ins[i].bytes) return invalid("the openings' extent is out of range");
+    const Span outs[] = {{"d_ob_enc", d_ob_enc, N * w_enc * 8},
+                         {"d_ob_mlwe", d_ob_mlwe, N * w_ml * 8},
+                         {"d_pf_incom", d_pf_incom, N * w_inc * 8},
+                         {"d_pf_partial", d_pf_partial, N * (p.cols + 1) * pq * 8},
+                         {"d_scratch", d_scratch, S.words * 8}};
+    RG_TRY(check_disjoint(who, outs, 5, ins, 5));
+  }
+  RG_TRY(on_device(J));
+  hipStream_t st = as_stream(stream);
+  uint64_t* scr = static_cast<uint64_t*>(d_scratch);
+  uint64_t *bq = scr + S.bq, *bo = scr + S.bo, *left = scr + S.left;
+  const long long ps = (long long)open_proof_stride, cs = (long long)open_commit_stride;
+  RG_TRY(point_multi(J, N, d_x, x_stride, left, nullptr, scr + S.lp, st));
+  if (batch == 1) {  // openBatch = open[0] (:267-269): InCommit copied, the partials straight from d_enc
+    hipLaunchKernelGGL(gather_kernel, dim3(grid256((long long)w_inc), (unsigned)N), dim3(256), 0, st, d_incom,
+                       ps * (long long)w_inc, d_pf_incom, (long long)w_inc);
+    RG_TRY(check_launch("jindo eval multi incommit"));
+    PDotArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = p.d, a.nl = p.nq, a.T = p.rows, a.nout = p.cols + 1;
+    a.A = left, a.a_proof = (long long)p.rows * pq, a.a_term = pq;
+    a.B = d_enc, a.b_proof = ps * (long long)w_enc, a.b_out = (long long)p.rows * pq, a.b_term = pq;
+    a.out = d_pf_partial;
+    return launch_pdot(a, J->rq, N, st);
+  }
+  // batch[i] into ringQ and ringQOut (:228-252)
+  RG_TRY(rg_jindo_encode_challenges_dev(J, 0, d_batch_bytes, N * batch, bq, stream));
+  RG_TRY(rg_jindo_encode_challenges_dev(J, 1, d_batch_bytes, N * batch, bo, stream));
+  {  // openBatch.InCommit and openBatch.MLWE (:254-266), a J = 1 dot product over the proof's commits
+    PDotArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = p.d, a.nl = p.nqo, a.T = (int)batch, a.nout = p.dcmp;
+    a.A = bo, a.a_proof = (long long)(batch * po), a.a_term = po;
+    a.B = d_incom, a.b_proof = ps * (long long)w_inc, a.b_out = po, a.b_term = cs * (long long)w_inc;
+    a.out = d_pf_incom;
+    RG_TRY(launch_pdot(a, J->ro, N, st));
+    a.nl = p.nq, a.nout = (int)((p.cols + 1) * nm);
+    a.A = bq, a.a_proof = (long long)(batch * pq), a.a_term = pq;
+    a.B = d_mlwe, a.b_proof = ps * (long long)w_ml, a.b_out = pq, a.b_term = cs * (long long)w_ml;
+    a.out = d_ob_mlwe;
+    RG_TRY(launch_pdot(a, J->rq, N, st));
+  }
+  EvalOpenArgs e;
+  memset(&e, 0, sizeof(e));
+  e.d = p.d, e.nl = p.nq, e.rows = p.rows, e.cols = p.cols, e.batch = (int)batch;
+  e.enc = d_enc, e.enc_proof = ps * (long long)w_enc, e.enc_commit = cs * (long long)w_enc;
+  e.bq = bq, e.left = left, e.ob_enc = d_ob_enc, e.partial = d_pf_partial;
+  for (int l = 0; l < p.nq; ++l) e.P[l] = J->rq[l];
+  return launch_eval_open(e, N, st);
+}
+
+size_t rg_jindo_eval_respond_multi_scratch_bytes(const rg_jindo* J, size_t n_proofs) {
+  if (!J || n_proofs == 0 || n_proofs > RG_JINDO_EVAL_MAX_PROOFS) return 0;
+  return n_proofs * J->p.cols * J->p.nq * J->p.d * 8;  // chals [N][cols][nq][d]
+}
+
+rg_status rg_jindo_eval_respond_multi_dev(const rg_jindo* J, size_t n_proofs, const uint64_t* d_ob_enc,
+                                          const uint64_t* d_ob_mlwe, size_t ob_proof_stride,
+                                          const uint8_t* d_chal_bytes, uint64_t* d_pf_enc, uint64_t* d_pf_mlwe,
+                                          void* d_scratch, void* stream) {
+  static const char who[] = "jindo eval multi respond";
+  auto invalid = [&](const std::string& why) {
+    set_last_error(std::string(who) + ": " + why);
+    return RG_ERR_INVALID;
+  };
+  if (!J) return invalid("NULL handle");
+  if (n_proofs == 0 || n_proofs > RG_JINDO_EVAL_MAX_PROOFS)
+    return invalid("n_proofs " + std::to_string(n_proofs) + " is not in [1, RG_JINDO_EVAL_MAX_PROOFS]");
+  if (!d_ob_enc || !d_ob_mlwe || !d_chal_bytes) return invalid("NULL d_ob_enc, d_ob_mlwe or d_chal_bytes");
+  if (ob_proof_stride == 0 || ob_proof_stride > kEvalMaxStride) return invalid("ob_proof_stride is not in [1, 2^31]");
+  if (!d_pf_enc || !d_pf_mlwe || !d_scratch) return invalid("NULL d_pf_enc, d_pf_mlwe or d_scratch");
+  const rg_jindo_params& p = J->p;
+  uint64_t bound = 0;
+  if (rg_jindo_challenge_bound(&p, &bound) != RG_OK) return invalid("ChallengeBound() is 0 (exp > 120)");
+  if ((unsigned long long)n_proofs * p.cols > 0x7fffffffull) return invalid("n_proofs * cols out of range");
+  const size_t N = n_proofs, pq = (size_t)p.nq * p.d, nm = (size_t)p.in_msis + p.mlwe;
+  const size_t w_enc = (size_t)(p.cols + 1) * p.rows * pq, w_ml = (size_t)(p.cols + 1) * nm * pq;
+  {
+    const unsigned __int128 openings = (unsigned __int128)(N - 1) * ob_proof_stride + 1;
+    const Span ins[] = {{"d_ob_enc", d_ob_enc, strided_bytes(openings, w_enc)},
+                        {"d_ob_mlwe", d_ob_mlwe, strided_bytes(openings, w_ml)},
+                        {"d_chal_bytes", d_chal_bytes, N * p.cols * 16}};
+    if (!ins[0].bytes || !ins[1].bytes) return invalid("the openBatches' extent is out of range");
+    const Span outs[] = {{"d_pf_enc", d_pf_enc, N * p.rows * pq * 8},
+                         {"d_pf_mlwe", d_pf_mlwe, N * nm * pq * 8},
+                         {"d_scratch", d_scratch, N * p.cols * pq * 8}};
+    RG_TRY(check_disjoint(who, outs, 3, ins, 3));
+  }
+  RG_TRY(on_device(J));
+  hipStream_t st = as_stream(stream);
+  uint64_t* chals = static_cast<uint64_t*>(d_scratch);
+  RG_TRY(rg_jindo_encode_challenges_dev(J, 0, d_chal_bytes, N * p.cols, chals, stream));
+  const long long ps = (long long)ob_proof_stride;
+  PDotArgs a;
+  memset(&a, 0, sizeof(a));
+  // pf.Encode[i] = Enc[cols][i] + sum_j chals[j] * Enc[j][i] (prover.go:300-306)
+  a.d = p.d, a.nl = p.nq, a.T = p.cols, a.nout = p.rows;
+  a.A = chals, a.a_proof = (long long)(p.cols * pq), a.a_term = pq;
+  a.B = d_ob_enc, a.b_proof = ps * (long long)w_enc, a.b_out = pq, a.b_term = (long long)(p.rows * pq);
+  a.C = d_ob_enc + (size_t)p.cols * p.rows * pq, a.c_proof = a.b_proof, a.c_out = pq;
+  a.out = d_pf_enc;
+  RG_TRY(launch_pdot(a, J->rq, N, st));
+  // pf.MLWE[i] = MLWE[cols][i] + sum_j chals[j] * MLWE[j][i] (:308-314)
+  a.nout = (int)nm;
+  a.B = d_ob_mlwe, a.b_proof = ps * (long long)w_ml, a.b_term = (long long)(nm * pq);
+  a.C = d_ob_mlwe + (size_t)p.cols * nm * pq, a.c_proof = a.b_proof;
+  a.out = d_pf_mlwe;
+  return launch_pdot(a, J->rq, N, st);
+}
+
+}  // extern "C"

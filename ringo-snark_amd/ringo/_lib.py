@@ -217,6 +217,11 @@ _SIGS = {
     "rg_jindo_verify_inputs_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
     "rg_jindo_verify_inputs_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t] +
                                          [vp] * 9),
+    "rg_jindo_eval_open_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t, ctypes.c_size_t]),
+    "rg_jindo_eval_open_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t,
+                                                    ctypes.c_size_t, vp, ctypes.c_size_t] + [vp] * 7),
+    "rg_jindo_eval_respond_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_jindo_eval_respond_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t] + [vp] * 5),
     "rg_malloc": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_size_t]),
     "rg_free": (ctypes.c_int, [vp]),
     "rg_memcpy_h2d": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp]),

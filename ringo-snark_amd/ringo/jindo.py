@@ -352,6 +352,48 @@ class Prover:
         check(lib().rg_jindo_encode_challenges_dev(self.h, ring, _byte_addr(bytes, 16 * n), n,
                                                    _addr(out, n * (P.nqo if ring else P.nq) * P.d), _stream(stream)))
 
+    # ---- Evaluate for n_proofs proofs in two asynchronous calls around the transcript ----
+    def eval_open_multi_scratch_bytes(self, n_proofs, batch):
+        """Bytes of scratch eval_open_multi_dev needs (0 for arguments the call would refuse)."""
+        return lib().rg_jindo_eval_open_multi_scratch_bytes(self.h, n_proofs, batch)
+
+    def eval_open_multi_dev(self, n_proofs, batch, incom, enc, mlwe, open_proof_stride, open_commit_stride, x,
+                            x_stride, batch_bytes, ob_enc, ob_mlwe, pf_incom, pf_partial, scratch, stream=None):
+        """openBatch and Proof.InCommit / Partial / PartialMask of n_proofs proofs in one asynchronous call
+        (rg_jindo_eval_open_multi_dev): opening t of proof p is open_proof_stride * p + open_commit_stride * t
+        openings into incom / enc / mlwe, x and x_stride as eval_point_multi_dev, batch_bytes
+        [n_proofs][batch][16] uint8; into ob_enc [n][cols+1][rows][nq][d], ob_mlwe [n][cols+1][nm][nq][d],
+        pf_incom [n][dcmp][nqo][d], pf_partial [n][cols+1][nq][d].  batch_bytes = ob_enc = ob_mlwe = None iff
+        batch == 1; scratch holds eval_open_multi_scratch_bytes(n_proofs, batch) bytes."""
+        P, n, es = self.params, n_proofs, self.eval_shapes()
+        last = ((n - 1) * open_proof_stride + (batch - 1) * open_commit_stride + 1) if n and batch else 0
+        check(lib().rg_jindo_eval_open_multi_dev(
+            self.h, n, batch, _addr(incom, last * _words(es["ob_incom"])), _addr(enc, last * _words(es["ob_enc"])),
+            _addr(mlwe, last * _words(es["ob_mlwe"])), open_proof_stride, open_commit_stride,
+            _addr(x, ((n - 1) * x_stride + 1) * P.L if n else None), x_stride, _byte_addr(batch_bytes, n * batch * 16),
+            _addr(ob_enc, n * _words(es["ob_enc"])), _addr(ob_mlwe, n * _words(es["ob_mlwe"])),
+            _addr(pf_incom, n * _words(es["ob_incom"])), _addr(pf_partial, n * _words(es["partial"])),
+            _addr(scratch, self.eval_open_multi_scratch_bytes(n, batch) // 8), _stream(stream)))
+
+    def eval_respond_multi_scratch_bytes(self, n_proofs):
+        """Bytes of scratch eval_respond_multi_dev needs (0 for an n_proofs outside [1, EVAL_MAX_PROOFS])."""
+        return lib().rg_jindo_eval_respond_multi_scratch_bytes(self.h, n_proofs)
+
+    def eval_respond_multi_dev(self, n_proofs, ob_enc, ob_mlwe, ob_proof_stride, chal_bytes, pf_enc, pf_mlwe, scratch,
+                               stream=None):
+        """Proof.Encode and Proof.MLWE of n_proofs proofs in one asynchronous call
+        (rg_jindo_eval_respond_multi_dev): the openBatch of proof p is ob_proof_stride * p openings into ob_enc /
+        ob_mlwe (1 after eval_open_multi_dev; the openings and their proof stride when batch == 1), chal_bytes
+        [n_proofs][cols][16] uint8; into pf_enc [n][rows][nq][d], pf_mlwe [n][nm][nq][d]; scratch holds
+        eval_respond_multi_scratch_bytes(n_proofs) bytes."""
+        P, n, es = self.params, n_proofs, self.eval_shapes()
+        last = (n - 1) * ob_proof_stride + 1 if n else 0
+        check(lib().rg_jindo_eval_respond_multi_dev(
+            self.h, n, _addr(ob_enc, last * _words(es["ob_enc"])), _addr(ob_mlwe, last * _words(es["ob_mlwe"])),
+            ob_proof_stride, _byte_addr(chal_bytes, n * P.cols * 16), _addr(pf_enc, n * _words(es["pf_enc"])),
+            _addr(pf_mlwe, n * _words(es["pf_mlwe"])), _addr(scratch, self.eval_respond_multi_scratch_bytes(n) // 8),
+            _stream(stream)))
+
     def challenge_bound(self):
         """Parameters.ChallengeBound() (params.go:357-360)."""
         b, ps = ctypes.c_uint64(), self.params.c_struct()
@@ -386,6 +428,8 @@ VERIFY_MAX_PROOFS = 65535
 VERIFY_WORDS = 54
 # include/ringo.h RG_JINDO_POINT_MAX_POINTS (tests/test_capi_jindo_verify_inputs.py)
 POINT_MAX_POINTS = 65535
+# include/ringo.h RG_JINDO_EVAL_MAX_PROOFS (tests/test_capi_jindo_eval_multi.py)
+EVAL_MAX_PROOFS = 65535
 
 
 @dataclass
