@@ -595,6 +595,99 @@ rg_status rg_buckler_sumcheck_mask_batch(const rg_field* f, size_t rank, size_t 
                                          size_t n_proofs, const uint64_t* rand, uint64_t* mask, uint64_t* mask_com,
                                          uint64_t* mask_sum);
 
+/* ---- Buckler prover's witness rounds for a batch of proofs (prover.go:77-111, 136-153, 195-201) ---- */
+/* What Prove does to its witness table before its first commit and at each commit round, for n_proofs
+ * proofs of one compiled circuit and in the vocabulary of rg_buckler_prove_proj_round_dev: every array
+ * proof-major, Montgomery and canonical, every argument validated before the device is touched
+ * (rg_last_error has the reason), everything asynchronous on `stream`, nothing allocated, copied back or
+ * waited for inside (one exception below), every output word written by exactly one writer, no atomics,
+ * a launch count without n_proofs in it.  n_proofs = 0 does nothing; n_proofs > RG_BK_MULTI_MAX_PROOFS
+ * (or a table above 2^44 words) and any two aliased buffers are RG_ERR_INVALID; a limb count other than
+ * 1, 2, 4, 7, 14 is RG_ERR_UNSUPPORTED.  The transcript, the XOF, SetBytes, decomposeBase and pwBase /
+ * pwMask stay with the caller.  With both rounds a witness table stays on the device, in one layout,
+ * from the assignment to the d_w of rg_buckler_prove_checks_dev.
+ *
+ * Creating either handle touches no device.  A handle's own small table (the digit-row IDs, the
+ * selected rows) reaches the device by the first-use rule of rg_dcmp: the first call that runs a kernel
+ * uploads it, to the device current then, and waits for that copy; the borrowed rg_dcmp handles upload
+ * their bases under their own rule in the same call (capture a graph only after it).  Calls on different
+ * streams use different scratch and may share a handle.  The forms without `_dev` take host pointers
+ * and are synchronous.
+ *
+ * The decomposition round (prover.go:77-111).  The handle holds what Compile fixes: the field, the
+ * witness rank, the number of witnesses n_w of the table,
+ *   - n_inf infinity-norm constraints (context.go:136-145): inf_src [n_inf] the witness IDs,
+ *     inf_dcmp [n_inf] the borrowed rg_dcmp of decomposeBase(bound) of each, and inf_rows, the digit-row
+ *     IDs wDcmp[j] of all constraints one after the other, nb(c) of constraint c in base order (nb(c) is
+ *     inf_dcmp[c]'s).  Compile makes the rows of a constraint consecutive; any distinct rows are taken.
+ *   - n_two two-norm constraints (context.go:171-185): two_cons [n_two][2] = (src, dst) and two_dcmp
+ *     [n_two] the borrowed rg_dcmp of each.
+ * RG_ERR_INVALID for n_inf + n_two = 0, n_inf > 32 or n_two > 32 (the constraint tables travel as kernel
+ * arguments; the digit-row IDs, up to several hundred a constraint, live on the device), an index >=
+ * n_w, an rg_dcmp of another field, nb > rank for a two-norm constraint, rank 0 or above 2^30, and an
+ * output row (a digit row or a dst) that is another output row or any constraint's src: the reference
+ * ranges over maps there (prover.go:77, 89), so no order is defined that a result could depend on.
+ * Several constraints may share one src.
+ *
+ * d_w [n_proofs][n_w][rank][L]: the plain witness table as wData.w holds it, read and written in place.
+ * For every proof and infinity-norm constraint, digit row j becomes digit j of every coefficient of
+ * w[src], the elements rg_buckler_dcmp_inf_dev writes.  For every proof and two-norm constraint, row dst
+ * gets the digits of sqNm = sum_i plain(w[src]_i)^2 mod q in entries 0 .. nb - 1 and zeros above, as
+ * rg_buckler_dcmp_two_dev writes them.  d_sq (optional, NULL for a handle with n_two = 0)
+ * [n_proofs][n_two][L]: sqNm in Montgomery form.  Every other row of d_w is left untouched.
+ *
+ * Three launches (one with n_two = 0, two with n_inf = 0): the digits of all proofs and infinity-norm
+ * constraints, a lane per coefficient; the squares of all proofs and two-norm constraints summed per
+ * workgroup of 1024 coefficients into scratch; those sums added in chunk order, decomposed and stored
+ * with the zero tail.  d_scratch holds rg_buckler_prove_dcmp_round_scratch_bytes(h, n_proofs) =
+ * n_proofs * n_two * ceil(rank / 1024) * L * 8 bytes (0 for an n_proofs that is refused; d_scratch may be
+ * NULL when n_two = 0). */
+typedef struct rg_bdcmp rg_bdcmp;
+rg_status rg_buckler_dcmp_round_create(const rg_field* f, size_t rank, size_t n_w, size_t n_inf,
+                                       const uint64_t* inf_src, const rg_dcmp* const* inf_dcmp,
+                                       const uint64_t* inf_rows, size_t n_two, const uint64_t* two_cons,
+                                       const rg_dcmp* const* two_dcmp, rg_bdcmp** out);
+void rg_buckler_dcmp_round_destroy(rg_bdcmp* h);
+size_t rg_buckler_prove_dcmp_round_scratch_bytes(const rg_bdcmp* h, size_t n_proofs);
+rg_status rg_buckler_prove_dcmp_round_dev(const rg_bdcmp* h, size_t n_proofs, uint64_t* d_w, uint64_t* d_sq,
+                                          uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_prove_dcmp_round(const rg_bdcmp* h, size_t n_proofs, uint64_t* w, uint64_t* sq);
+/* The encode round (prover.go:136-153, 195-201): wEcd[i] = RandEncode(w[i]) for the rows of one commit
+ * round, the first-round rows or ctx.wSecond after the projection round; a prover makes one handle per
+ * round.  The handle holds the encoder's cyclic plan at the witness rank (borrowed; a negacyclic plan is
+ * RG_ERR_INVALID), the embedding rank (a power of two above the rank, at most 2^30), n_w and sel
+ * [n_sel], the rows of this round: distinct, each < n_w, in any order, 1 <= n_sel <= 65535.
+ *
+ * d_w [n_proofs][n_w][rank][L]: the plain table.  d_rand [n_proofs][n_sel][L]: the MustSetRandom draws
+ * in sel order; NULL means EncodeTo, so the public witnesses' table can use the same entry.  d_wecd
+ * [n_proofs][n_w][emb][L].  d_com (optional) [n_proofs][n_sel][rank + 1][L]; d_com with d_rand NULL is
+ * RG_ERR_INVALID.  For every proof and s < n_sel, row sel[s] of d_wecd becomes RandEncode(w[sel[s]]):
+ * the cyclic InvNTT in coefficients 0 .. rank - 1, coeff[rank] = r, coeff[0] -= r, zeros above, the
+ * elements rg_buckler_encode_dev writes; d_com[proof][s] gets its first rank + 1 coefficients,
+ * contiguous, which is the input of rg_jindo_commit_dev with batch = n_proofs * n_sel and nv = rank + 1.
+ * Rows of d_wecd outside sel are left untouched.
+ *
+ * Two launches plus the plan's own: one gather of the selected rows into scratch (skipped when sel is
+ * 0 .. n_w - 1, and then the table itself is the transform's input), one batched rg_ntt_inv_dev over
+ * the n_proofs * n_sel vectors, one kernel that writes the strided d_wecd rows and the d_com rows
+ * together.  d_scratch holds rg_buckler_prove_encode_round_scratch_bytes(h, n_proofs) =
+ * n_proofs * n_sel * rank * L * 8 bytes (0 for an n_proofs that is refused).
+ *
+ * The forward transform is deliberately not in this call: wEcdNTT is first read by the checks, after
+ * the last commit round (prover.go:242-334).  So once both rounds have written d_wecd the caller runs
+ * ONE in-place rg_ntt_fwd_dev(emb_plan, d_wecd, d_wecd, n_proofs * n_w) over the whole contiguous
+ * table; the result is the d_w of rg_buckler_prove_checks_dev. */
+typedef struct rg_bencode rg_bencode;
+rg_status rg_buckler_encode_round_create(const rg_ntt* enc_plan, size_t emb_rank, size_t n_w, size_t n_sel,
+                                         const uint64_t* sel, rg_bencode** out);
+void rg_buckler_encode_round_destroy(rg_bencode* h);
+size_t rg_buckler_prove_encode_round_scratch_bytes(const rg_bencode* h, size_t n_proofs);
+rg_status rg_buckler_prove_encode_round_dev(const rg_bencode* h, size_t n_proofs, const uint64_t* d_w,
+                                            const uint64_t* d_rand, uint64_t* d_wecd, uint64_t* d_com,
+                                            uint64_t* d_scratch, void* stream);
+rg_status rg_buckler_prove_encode_round(const rg_bencode* h, size_t n_proofs, const uint64_t* w, const uint64_t* rand,
+                                        uint64_t* wecd, uint64_t* com);
+
 /* ------------------------------------------------------------------------------------ */
 /* Jindo commitment (jindo/params.go, encoder.go, rns.go, prover.go, entities.go)         */
 /* ------------------------------------------------------------------------------------ */

@@ -175,6 +175,19 @@ _SIGS = {
     "rg_buckler_prove_proj_round": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, ctypes.c_char_p]),
     "rg_buckler_sumcheck_mask_batch_dev": (ctypes.c_int, [vp] + [ctypes.c_size_t] * 4 + [vp] * 5),
     "rg_buckler_sumcheck_mask_batch": (ctypes.c_int, [vp] + [ctypes.c_size_t] * 4 + [u64p] * 4),
+    "rg_buckler_dcmp_round_create": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p,
+                                                    ctypes.POINTER(vp), u64p, ctypes.c_size_t, u64p,
+                                                    ctypes.POINTER(vp), ctypes.POINTER(vp)]),
+    "rg_buckler_dcmp_round_destroy": (None, [vp]),
+    "rg_buckler_prove_dcmp_round_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_buckler_prove_dcmp_round_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, vp, vp]),
+    "rg_buckler_prove_dcmp_round": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p]),
+    "rg_buckler_encode_round_create": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p,
+                                                      ctypes.POINTER(vp)]),
+    "rg_buckler_encode_round_destroy": (None, [vp]),
+    "rg_buckler_prove_encode_round_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
+    "rg_buckler_prove_encode_round_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp]),
+    "rg_buckler_prove_encode_round": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, u64p, u64p, u64p]),
     "rg_jindo_create": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), u64p, u64p, u64p, ctypes.POINTER(vp)]),
     "rg_jindo_create_from_crs": (ctypes.c_int, [ctypes.POINTER(JindoParamsC), ctypes.c_char_p, ctypes.c_size_t,
                                                 ctypes.POINTER(vp)]),

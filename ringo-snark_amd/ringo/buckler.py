@@ -40,6 +40,14 @@ and what stands between the commit rounds before them (buckler/prover.go:165-240
     proj = ProjRoundPlan(F, rank, nW, [(src, projID, dcmpID, Decomposer(F, rank * bound))])
     w = proj.round(w, xof)                                     # the proj and dcmp rows of every proof
     masks, maskComs, maskSums = SumCheckMaskBatch(F, rank, maskRank, embRank, rand)
+
+and what stands before the first commit and at each commit round (buckler/prover.go:77-111, 136-153,
+195-201), on the same proof-major table:
+
+    dcmp = DcmpRoundPlan(F, rank, nW, inf=[(src, bound, [digit rows])], two=[(src, bound, dst)])
+    w, sqNm = dcmp.round(w)                                    # the digit and dst rows of every proof
+    enc = EncodeRoundPlan(F, rank, embRank, nW, sel)           # sel: the rows of this commit round
+    wEcd, comPolys = enc.round(w, rand, wEcd)                  # RandEncode of rows sel, Coeffs[:rank+1] contiguous
 """
 import ctypes
 
@@ -959,6 +967,115 @@ class Decomposer:
             self.h, _addr(d_w, n), batch, rank, _addr(d_out, n), _addr(d_sq, batch * L) if d_sq is not None else None,
             _addr(d_scratch, self.scratch_bytes(batch, rank) // 8) if d_scratch is not None else None,
             _stream(stream)))
+
+
+# ---- the witness rounds for a batch of proofs (buckler/prover.go:77-111, 136-153, 195-201) ------------
+def _u64s(xs):
+    return (ctypes.c_uint64 * max(1, len(xs)))(*xs)
+
+
+class DcmpRoundPlan:
+    """What the norm decompositions (prover.go:77-111) take from the compiled context (rg_bdcmp): the
+    witness rank, the number of witnesses nW of the table, the infinity-norm constraints as (src, bound,
+    [digit rows]) and the two-norm constraints as (src, bound, dst).  A bound is an int (the base is
+    decomposeBase(bound)) or a Decomposer; an infinity-norm constraint has one digit row per base element."""
+
+    def __init__(self, field, rank, nW, inf=(), two=()):
+        self.field, self.rank, self.nW = field, rank, nW
+
+        def dcmp(b):  # the decomposers kept alive: the handle borrows them
+            return b if isinstance(b, Decomposer) else Decomposer(field, b)
+
+        self.inf = [(int(s), dcmp(b), [int(r) for r in rows]) for s, b, rows in inf]
+        self.two = [(int(s), dcmp(b), int(d)) for s, b, d in two]
+        for _, dc, rows in self.inf:
+            if len(rows) != len(dc.dcmpBase):
+                raise RingoPanic("inconsistent input(s)")  # one digit row per base element
+        h = vp()
+        _status(lib().rg_buckler_dcmp_round_create(
+            field.h, rank, nW, len(self.inf), _u64s([s for s, _, _ in self.inf]),
+            (vp * max(1, len(self.inf)))(*[dc.h.value for _, dc, _ in self.inf]),
+            _u64s([r for _, _, rows in self.inf for r in rows]), len(self.two),
+            _u64s([i for s, _, d in self.two for i in (s, d)]),
+            (vp * max(1, len(self.two)))(*[dc.h.value for _, dc, _ in self.two]), ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_buckler_dcmp_round_destroy(self.h)
+            self.h = None
+
+    def scratch_bytes(self, n_proofs):
+        return lib().rg_buckler_prove_dcmp_round_scratch_bytes(self.h, n_proofs)
+
+    def round_dev(self, n_proofs, d_w, d_sq=None, d_scratch=None, stream=None):
+        """rg_buckler_prove_dcmp_round_dev: d_w [n][nW][rank][L], the plain witness table, whose digit and
+        dst rows are written in place; d_sq (optional) [n][n_two][L].  Asynchronous on `stream`."""
+        n, L = n_proofs, self.field.L
+        _status(lib().rg_buckler_prove_dcmp_round_dev(
+            self.h, n, _addr(d_w, n * self.nW * self.rank * L),
+            _addr(d_sq, n * len(self.two) * L) if d_sq is not None else None,
+            _addr(d_scratch, self.scratch_bytes(n) // 8) if d_scratch is not None else None, _stream(stream)))
+
+    def round(self, w):
+        """rg_buckler_prove_dcmp_round (host arrays, synchronous): w [n][nW][rank][L] -> (the table with
+        the digit and dst rows of every proof filled in (a copy), sqNm [n][n_two][L] in Montgomery form,
+        or None without a two-norm constraint)."""
+        w = np.array(np.asarray(w, np.uint64).reshape(-1, self.nW, self.rank, self.field.L), order="C")
+        n = w.shape[0]
+        sq = np.zeros((max(n, 1), len(self.two), self.field.L), np.uint64) if self.two else None
+        _status(lib().rg_buckler_prove_dcmp_round(self.h, n, ptr(w), ptr(sq)))
+        return w, (None if sq is None else sq[:n])
+
+
+class EncodeRoundPlan:
+    """What the encodings of one commit round (prover.go:136-153, 195-201) take from the compiled context
+    (rg_bencode): the witness rank, the embedding rank, the number of witnesses nW of the table and `sel`,
+    the rows of this round (the first-round rows, or ctx.wSecond)."""
+
+    def __init__(self, field, rank, embRank, nW, sel):
+        self.field, self.rank, self.embRank, self.nW = field, rank, embRank, nW
+        self.sel = [int(s) for s in sel]
+        self.ntt = NewCyclicTransformer(field, rank)  # kept alive: the handle borrows it
+        h = vp()
+        _status(lib().rg_buckler_encode_round_create(self.ntt.h, embRank, nW, len(self.sel), _u64s(self.sel),
+                                                     ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_buckler_encode_round_destroy(self.h)
+            self.h = None
+
+    def scratch_bytes(self, n_proofs):
+        return lib().rg_buckler_prove_encode_round_scratch_bytes(self.h, n_proofs)
+
+    def round_dev(self, n_proofs, d_w, d_wecd, d_rand=None, d_com=None, d_scratch=None, stream=None):
+        """rg_buckler_prove_encode_round_dev: d_w [n][nW][rank][L] -> rows `sel` of d_wecd [n][nW][embRank][L]
+        and, when given, d_com [n][n_sel][rank + 1][L]; d_rand [n][n_sel][L] or None (EncodeTo).
+        Asynchronous on `stream`."""
+        n, L, ns = n_proofs, self.field.L, len(self.sel)
+        _status(lib().rg_buckler_prove_encode_round_dev(
+            self.h, n, _addr(d_w, n * self.nW * self.rank * L),
+            _addr(d_rand, n * ns * L) if d_rand is not None else None, _addr(d_wecd, n * self.nW * self.embRank * L),
+            _addr(d_com, n * ns * (self.rank + 1) * L) if d_com is not None else None,
+            _addr(d_scratch, self.scratch_bytes(n) // 8) if d_scratch is not None else None, _stream(stream)))
+
+    def round(self, w, rand=None, wecd=None):
+        """rg_buckler_prove_encode_round (host arrays, synchronous): w [n][nW][rank][L], rand [n][n_sel][L]
+        or None, wecd [n][nW][embRank][L] (the table so far; zeros when None) -> (wecd with the rows `sel`
+        of every proof filled in (a copy), com [n][n_sel][rank + 1][L], or None without rand)."""
+        L, ns = self.field.L, len(self.sel)
+        w = np.ascontiguousarray(np.asarray(w, np.uint64).reshape(-1, self.nW, self.rank, L))
+        n = w.shape[0]
+        r = None if rand is None else np.ascontiguousarray(np.asarray(rand, np.uint64).reshape(n, ns, L))
+        out = np.zeros((n, self.nW, self.embRank, L), np.uint64) if wecd is None else \
+            np.array(np.asarray(wecd, np.uint64).reshape(n, self.nW, self.embRank, L), order="C")
+        com = None if r is None else np.zeros((max(n, 1), ns, self.rank + 1, L), np.uint64)
+        _status(lib().rg_buckler_prove_encode_round(self.h, n, ptr(w), ptr(r), ptr(out), ptr(com)))
+        return out, (None if com is None else com[:n])
 
 
 def TwoNormPublic(field, rank, bound):
