@@ -595,6 +595,59 @@ rg_status rg_buckler_sumcheck_mask_batch(const rg_field* f, size_t rank, size_t 
                                          size_t n_proofs, const uint64_t* rand, uint64_t* mask, uint64_t* mask_com,
                                          uint64_t* mask_sum);
 
+/* ---- Buckler prover's MustSetRandom draws on the device (element.go:299-343) ---- */
+/* A field-element sampler on any built field: NewUniformSamplerWithSeed(seed) in place of crypto/rand,
+ * as rg_jindo_seeds.uniform is for a Jindo handle.  Element i of d_out [n][L] is Uint.SetRandom reading
+ * from instance first_instance + i of that sampler (the instance windows of rg_jindo_sample_dev: IV +
+ * instance * 2^24): k = ceil(bitLen(q - 1) / 8) bytes, the top byte's unused bits cleared, rejected
+ * while >= q; the stored limbs are the accepted candidate's little-endian words, no domain conversion,
+ * as in the reference.  One element is one instance, so every value is a pure function of (seed,
+ * instance, q) and the partition of draws among instances is the caller's.
+ *
+ * Creating the handle touches no device; RG_ERR_UNSUPPORTED where libcrypto's SHA-384 is missing and
+ * for a limb count other than 1, 2, 4, 7, 14.  The handle's AES table reaches the device by the
+ * first-use rule of rg_dcmp: the first call that runs a kernel uploads it, to the device current then,
+ * and waits for that copy (capture a graph only after it).  Apart from that the `_dev` entry is
+ * asynchronous on `stream`: nothing is allocated, freed, copied to the host or waited for inside, and
+ * the handle is only read, so calls on different streams with different scratch are independent.
+ * Stream items, whatever n: 3 on the whole-word route (even L with k = 8 L, e.g. q255: a 4-byte memset
+ * of the long-draw flag in d_scratch, the draws, the long draws' fix-up), 1 on the byte-serial route
+ * (every other field).  d_scratch holds rg_field_sampler_scratch_bytes(s) = 256 bytes.
+ *
+ * n = 0 returns RG_OK and touches nothing.  RG_ERR_INVALID, before the device is touched and with a
+ * reason in rg_last_error that starts "field sampler": a NULL handle, output or scratch; first_instance
+ * + n passing 2^64 - 1 (or n above 2^44); d_out overlapping d_scratch.  The form without `_dev` takes
+ * a host pointer and is synchronous. */
+typedef struct rg_fsampler rg_fsampler;
+rg_status rg_field_sampler_create(const rg_field* f, const uint8_t* seed, size_t seed_len, rg_fsampler** out);
+void rg_field_sampler_destroy(rg_fsampler* s);
+size_t rg_field_sampler_scratch_bytes(const rg_fsampler* s);
+rg_status rg_field_sampler_elems_dev(const rg_fsampler* s, unsigned long long first_instance, size_t n,
+                                     uint64_t* d_out, void* d_scratch, void* stream);
+rg_status rg_field_sampler_elems(const rg_fsampler* s, unsigned long long first_instance, size_t n, uint64_t* out);
+/* Prover.sumCheckMask(maskRank) (prover.go:381-397) of n_proofs proofs with its draws made inside the
+ * mask kernel: draw k of proof p is the element of instance first_instance + p * mask_rank + k, and
+ * the outputs equal, word for word, rg_field_sampler_elems_dev(s, first_instance, n_proofs * mask_rank,
+ * d_rand) followed by rg_buckler_sumcheck_mask_batch_dev on that d_rand -- which never exists here.
+ * d_mask [n_proofs][emb_rank][L], d_mask_com (optional) [n_proofs][mask_rank][L], d_mask_sum
+ * [n_proofs][L] (draw 0, before the subtraction).  Every draw is made once (a lane walks k, k + rank,
+ * k + 2 rank, ... of one proof; mask_rank is not bounded by 2 rank), every output word, the zeros up
+ * to emb_rank included, has exactly one writer, no atomics.  Stream items, whatever n_proofs: 3 on the
+ * whole-word route, 1 on the byte-serial route.  d_scratch holds rg_field_sampler_scratch_bytes(s)
+ * bytes.  The constraints and refusals of rg_buckler_sumcheck_mask_batch_dev (rank <= mask_rank <=
+ * emb_rank, n_proofs <= RG_BK_MULTI_MAX_PROOFS, overlapping buffers), a NULL handle or scratch, and
+ * first_instance + n_proofs * mask_rank passing 2^64 - 1: RG_ERR_INVALID before the device is touched,
+ * the reason starting "buckler mask sampled".  n_proofs = 0 does nothing.  The first-use rule of the
+ * handle applies.  The form without `_dev` takes host pointers and is synchronous. */
+rg_status rg_buckler_sumcheck_mask_batch_sampled_dev(const rg_fsampler* s, size_t rank, size_t mask_rank,
+                                                     size_t emb_rank, size_t n_proofs,
+                                                     unsigned long long first_instance, uint64_t* d_mask,
+                                                     uint64_t* d_mask_com, uint64_t* d_mask_sum, void* d_scratch,
+                                                     void* stream);
+rg_status rg_buckler_sumcheck_mask_batch_sampled(const rg_fsampler* s, size_t rank, size_t mask_rank, size_t emb_rank,
+                                                 size_t n_proofs, unsigned long long first_instance, uint64_t* mask,
+                                                 uint64_t* mask_com, uint64_t* mask_sum);
+
 /* ---- Buckler prover's witness rounds for a batch of proofs (prover.go:77-111, 136-153, 195-201) ---- */
 /* What Prove does to its witness table before its first commit and at each commit round, for n_proofs
  * proofs of one compiled circuit and in the vocabulary of rg_buckler_prove_proj_round_dev: every array

@@ -249,6 +249,81 @@ struct Uniform {
   }
 };
 
+// ---- Uint.SetRandom (element.go:299-343) reading from one instance ---------------------------
+// Read k = ceil(bitLen(q - 1) / 8) bytes, clear the last byte's unused top bits (top_mask), reject
+// while >= q.  The one statement of the draw, by two routes, for every kernel that draws field
+// elements (jindo_sample.hip: lastRow and the mask column; buckler_sample.hip: any built field):
+//   whole words  even L with k = 8 L (e.g. q255: 32 bytes): a try is L / 2 whole AES blocks;
+//   byte-serial  every other field: bytes leave the Sample() words one at a time, and the unread
+//                bytes of a word carry into the instance's next try.
+// The accepted candidate's little-endian words are the result as they stand (no domain conversion).
+
+// the top word's mask of a whole-word draw
+__device__ __forceinline__ uint64_t set_random_topm(uint32_t top_mask) {
+  return ((uint64_t)top_mask << 56) | 0x00FFFFFFFFFFFFFFull;
+}
+
+// Try t of a whole-word draw within the instance's first 8 KiB ((t + 1) L <= 1024): blocks
+// t L / 2 .. of the window, in pairs in lockstep; true when z < q
+template <int L>
+__device__ __forceinline__ bool set_random_whole_try(LdsKey key, const uint32_t* lds, uint64_t inst, int t, uint64_t topm,
+                                                     const FieldParams<L>& F, uint64_t (&z)[L]) {
+  static_assert(L % 2 == 0, "whole 16-byte blocks per try");
+  if constexpr (L >= 4) {
+#pragma unroll
+    for (int h = 0; h < L / 4; ++h)
+      ks_words_x2(key, inst, (uint64_t)t * (L / 2) + 2 * h, (uint64_t)t * (L / 2) + 2 * h + 1, lds, z + 4 * h);
+  }
+  if constexpr (L % 4 != 0) ks_words(key, inst, (uint64_t)t * (L / 2) + (L / 2 - 1), lds, z[L - 2], z[L - 1]);
+  z[L - 1] &= topm;  // the last byte's unused top bits (element.go:320-325)
+  return !geq_q<L>(z, F);
+}
+
+// A whole-word draw to its end, the XOR-accumulated refill past the first 8 KiB included; returns
+// the number of tries
+template <int L>
+__device__ __forceinline__ uint64_t set_random_whole(LdsKey key, const uint32_t* lds, uint64_t inst, uint64_t topm,
+                                                     const FieldParams<L>& F, uint64_t (&z)[L]) {
+  for (uint64_t t = 0;; ++t) {
+    if ((t + 1) * L <= 1024) {
+#pragma unroll
+      for (int h = 0; h < L / 2; ++h) ks_words(key, inst, t * (L / 2) + h, lds, z[2 * h], z[2 * h + 1]);
+    } else {  // past the first 8 KiB buffer (uniform.go:64-82)
+#pragma unroll
+      for (int l = 0; l < L; ++l) z[l] = uniform_word_at(key, lds, inst, t * L + l);
+    }
+    z[L - 1] &= topm;  // the last byte's unused top bits (element.go:320-325)
+    if (!geq_q<L>(z, F)) return t + 1;
+  }
+}
+
+// A byte-serial draw to its end (Uniform::sample refills past the first 8 KiB)
+template <int L>
+__device__ __forceinline__ void set_random_bytes(const uint32_t* key_lds, const uint32_t* lds, uint64_t inst, int kbytes,
+                                                 uint32_t top_mask, const FieldParams<L>& F, uint64_t (&z)[L]) {
+  Uniform u;
+  u.init(key_lds, lds, inst);
+  uint64_t word = 0;
+  int left = 0;  // unread bytes of `word`
+  for (;;) {
+    el_zero<L>(z);
+    for (int j = 0; j < kbytes; ++j) {
+      if (!left) {
+        word = u.sample();
+        left = 8;
+      }
+      uint64_t byte = word & 255u;
+      word >>= 8;
+      --left;
+      if (j == kbytes - 1) byte &= top_mask;
+#pragma unroll
+      for (int l = 0; l < L; ++l)
+        if ((j >> 3) == l) z[l] |= byte << (8 * (j & 7));
+    }
+    if (!geq_q<L>(z, F)) return;
+  }
+}
+
 // slices.BinarySearch(table, u): smallest i with table[i] >= u; found -> i - 1 (twin_cdt.go:88-95)
 __device__ __forceinline__ int64_t cdt_search(const uint64_t* t, int n, uint64_t u) {
   int i = 0, j = n;

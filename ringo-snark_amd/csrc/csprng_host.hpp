@@ -16,6 +16,10 @@
 #include <cmath>
 #include <vector>
 
+#include "ck_crs.hpp"
+#include "common.hpp"
+#include "csprng.hpp"
+
 namespace rg {
 
 #pragma clang fp contract(off)
@@ -266,5 +270,34 @@ inline std::vector<double> compute_delta_inv(uint64_t base, int exp) {
 }
 
 #pragma clang fp contract(on)
+
+// ---- UniformSampler keys and Uint.SetRandom's byte count -------------------------------------
+// a UniformSampler's key from its seed: SHA-384 -> AES-256 key schedule + big-endian IV
+inline rg_status derive_key(const uint8_t* seed, size_t seed_len, AesKey& K) {
+  uint8_t r[48];
+  if (!sha384(seed, seed_len, r)) {
+    set_last_error("libcrypto SHA384 unavailable");
+    return RG_ERR_UNSUPPORTED;
+  }
+  aes256_expand(r, K.rk);
+  for (int w = 0; w < 4; ++w)
+    K.iv[w] = ((uint32_t)r[32 + 4 * w] << 24) | ((uint32_t)r[33 + 4 * w] << 16) | ((uint32_t)r[34 + 4 * w] << 8) |
+              r[35 + 4 * w];
+  return RG_OK;
+}
+
+// element.go:305-318: bitLen of q - 1, k bytes, top-byte mask
+inline void set_random_shape(const rg_field* f, int& kbytes, uint32_t& top_mask) {
+  uint64_t qm1[16];
+  memcpy(qm1, f->q, 8 * f->L);
+  for (int l = 0; l < f->L; ++l)
+    if (qm1[l]--) break;
+  int bitlen = 0;
+  for (int l = f->L - 1; l >= 0 && !bitlen; --l)
+    if (qm1[l]) bitlen = 64 * l + 64 - __builtin_clzll(qm1[l]);
+  kbytes = (bitlen + 7) / 8;
+  const int bb = bitlen % 8 ? bitlen % 8 : 8;
+  top_mask = (1u << bb) - 1u;
+}
 
 }  // namespace rg

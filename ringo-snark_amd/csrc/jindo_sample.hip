@@ -774,49 +774,14 @@ __global__ __launch_bounds__(512) void uniform_elems_kernel(UniArgs<L> a) {
     return;
   }
   const unsigned long long inst = (a.first_commit + (unsigned long long)b) * (unsigned long long)per + (unsigned long long)i;
-  if ((L % 2) == 0 && a.kbytes == 8 * L) {  // whole words (e.g. q255: 32 bytes): a try = L/2 blocks, in parallel
-    const uint64_t topm = ((uint64_t)a.top_mask << 56) | 0x00FFFFFFFFFFFFFFull;
-    for (uint64_t t = 0;; ++t) {
-      uint64_t z[L];
-      if ((t + 1) * L <= 1024) {
-#pragma unroll
-        for (int h = 0; h < L / 2; ++h) ks_words(LdsKey{key}, inst, t * (L / 2) + h, lds, z[2 * h], z[2 * h + 1]);
-      } else {  // past the first 8 KiB buffer (uniform.go:64-82)
-#pragma unroll
-        for (int l = 0; l < L; ++l) z[l] = uniform_word_at(LdsKey{key}, lds, inst, t * L + l);
-      }
-      z[L - 1] &= topm;  // the last byte's unused top bits (element.go:320-325)
-      if (!geq_q<L>(z, a.F)) {
-        el_copy<L>(dst, z);
-        return;
-      }
-    }
+  uint64_t z[L];
+  bool whole = false;  // whole words (e.g. q255: 32 bytes): a try = L/2 blocks, in parallel
+  if constexpr (L % 2 == 0) {
+    whole = a.kbytes == 8 * L;
+    if (whole) set_random_whole<L>(LdsKey{key}, lds, inst, set_random_topm(a.top_mask), a.F, z);
   }
-  Uniform u;
-  u.init(key, lds, inst);
-  uint64_t word = 0;
-  int left = 0;  // unread bytes of `word`
-  for (;;) {
-    uint64_t z[L];
-    el_zero<L>(z);
-    for (int j = 0; j < a.kbytes; ++j) {
-      if (!left) {
-        word = u.sample();
-        left = 8;
-      }
-      uint64_t byte = word & 255u;
-      word >>= 8;
-      --left;
-      if (j == a.kbytes - 1) byte &= a.top_mask;
-#pragma unroll
-      for (int l = 0; l < L; ++l)
-        if ((j >> 3) == l) z[l] |= byte << (8 * (j & 7));
-    }
-    if (!geq_q<L>(z, a.F)) {
-      el_copy<L>(dst, z);
-      return;
-    }
-  }
+  if (!whole) set_random_bytes<L>(key, lds, inst, a.kbytes, a.top_mask, a.F, z);
+  el_copy<L>(dst, z);
   }();
 }
 
@@ -870,16 +835,7 @@ __global__ __launch_bounds__(512) void uniform_whole_kernel(UniArgs<L> a, int* f
     uint64_t z[L];
     bool ok = false;
     if (max_tries > 0) {  // (0: every draw left to the fix-up, the experiments build's test)
-      if constexpr (L >= 4) {
-#pragma unroll
-        for (int h = 0; h < L / 4; ++h)
-          ks_words_x2(LdsKey{key}, inst, (uint64_t)t * (L / 2) + 2 * h, (uint64_t)t * (L / 2) + 2 * h + 1, lds,
-                      z + 4 * h);
-      }
-      if constexpr (L % 4 != 0)
-        ks_words(LdsKey{key}, inst, (uint64_t)t * (L / 2) + (L / 2 - 1), lds, z[L - 2], z[L - 1]);
-      z[L - 1] &= topm;  // the last byte's unused top bits (element.go:320-325)
-      ok = !geq_q<L>(z, a.F);
+      ok = set_random_whole_try<L>(LdsKey{key}, lds, inst, t, topm, a.F, z);
     }
     if (ok || t + 1 >= max_tries) {
       if (!ok) *flag = 1;
@@ -922,21 +878,9 @@ __global__ __launch_bounds__(512) void uniform_fix_kernel(UniArgs<L> a, const in
     for (int l = 0; l < L; ++l) ones = ones && dst[l] == ~0ull;
     if (!ones) continue;
     const unsigned long long inst = (a.first_commit + (unsigned long long)b) * (unsigned long long)per + (unsigned long long)i;
-    for (uint64_t t = 0;; ++t) {
-      uint64_t z[L];
-      if ((t + 1) * L <= 1024) {
-#pragma unroll
-        for (int h = 0; h < L / 2; ++h) ks_words(LdsKey{key}, inst, t * (L / 2) + h, lds, z[2 * h], z[2 * h + 1]);
-      } else {  // past the first 8 KiB buffer (uniform.go:64-82)
-#pragma unroll
-        for (int l = 0; l < L; ++l) z[l] = uniform_word_at(LdsKey{key}, lds, inst, t * L + l);
-      }
-      z[L - 1] &= topm;
-      if (!geq_q<L>(z, a.F)) {
-        el_copy<L>(dst, z);
-        break;
-      }
-    }
+    uint64_t z[L];
+    set_random_whole<L>(LdsKey{key}, lds, inst, topm, a.F, z);
+    el_copy<L>(dst, z);
   }
 }
 
@@ -958,20 +902,6 @@ __global__ __launch_bounds__(512) void uniform_words_kernel(AesKey key, const ui
 // ------------------------------------------------------------------------------------------
 // host: keys, launches, the sampler stage and its scratch
 // ------------------------------------------------------------------------------------------
-// a UniformSampler's key from its seed: SHA-384 -> AES-256 key schedule + big-endian IV
-static rg_status derive_key(const uint8_t* seed, size_t seed_len, AesKey& K) {
-  uint8_t r[48];
-  if (!sha384(seed, seed_len, r)) {
-    set_last_error("libcrypto SHA384 unavailable");
-    return RG_ERR_UNSUPPORTED;
-  }
-  aes256_expand(r, K.rk);
-  for (int w = 0; w < 4; ++w)
-    K.iv[w] = ((uint32_t)r[32 + 4 * w] << 24) | ((uint32_t)r[33 + 4 * w] << 16) | ((uint32_t)r[34 + 4 * w] << 8) |
-              r[35 + 4 * w];
-  return RG_OK;
-}
-
 static rg_status make_keys(const rg_jindo_seeds* seeds, AesKey* keys) {
   const uint8_t* sd[kNumDom] = {seeds->enc_cdt, seeds->enc_cosac, seeds->enc_cosac_round,
                                 seeds->mlwe_cdt, seeds->mlwe_round, seeds->uniform};
@@ -987,15 +917,7 @@ static rg_status launch_uniform(const rg_jindo* J, size_t batch, const AesKey& k
   a.key = key;
   a.te0 = J->smp.te0.as<uint32_t>();
   a.F = field_params<L>(&J->field);
-  // element.go:305-318: bitLen of q - 1, k bytes, top-byte mask
-  uint64_t qm1[16];
-  memcpy(qm1, J->field.q, 8 * L);
-  for (int l = 0; l < L; ++l)
-    if (qm1[l]--) break;
-  const int bitlen = bit_length(qm1, L);
-  a.kbytes = (bitlen + 7) / 8;
-  const int bb = bitlen % 8 ? bitlen % 8 : 8;
-  a.top_mask = (1u << bb) - 1u;
+  set_random_shape(&J->field, a.kbytes, a.top_mask);
   a.first_commit = first;
   a.last_row = last;
   a.mask = mask;

@@ -175,6 +175,15 @@ _SIGS = {
     "rg_buckler_prove_proj_round": (ctypes.c_int, [vp, ctypes.c_size_t, u64p, ctypes.c_char_p]),
     "rg_buckler_sumcheck_mask_batch_dev": (ctypes.c_int, [vp] + [ctypes.c_size_t] * 4 + [vp] * 5),
     "rg_buckler_sumcheck_mask_batch": (ctypes.c_int, [vp] + [ctypes.c_size_t] * 4 + [u64p] * 4),
+    "rg_field_sampler_create": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_field_sampler_destroy": (None, [vp]),
+    "rg_field_sampler_scratch_bytes": (ctypes.c_size_t, [vp]),
+    "rg_field_sampler_elems_dev": (ctypes.c_int, [vp, ctypes.c_ulonglong, ctypes.c_size_t, vp, vp, vp]),
+    "rg_field_sampler_elems": (ctypes.c_int, [vp, ctypes.c_ulonglong, ctypes.c_size_t, u64p]),
+    "rg_buckler_sumcheck_mask_batch_sampled_dev": (ctypes.c_int, [vp] + [ctypes.c_size_t] * 4 + [ctypes.c_ulonglong] +
+                                                   [vp] * 5),
+    "rg_buckler_sumcheck_mask_batch_sampled": (ctypes.c_int, [vp] + [ctypes.c_size_t] * 4 + [ctypes.c_ulonglong] +
+                                               [u64p] * 3),
     "rg_buckler_dcmp_round_create": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u64p,
                                                     ctypes.POINTER(vp), u64p, ctypes.c_size_t, u64p,
                                                     ctypes.POINTER(vp), ctypes.POINTER(vp)]),

@@ -48,6 +48,12 @@ and what stands before the first commit and at each commit round (buckler/prover
     w, sqNm = dcmp.round(w)                                    # the digit and dst rows of every proof
     enc = EncodeRoundPlan(F, rank, embRank, nW, sel)           # sel: the rows of this commit round
     wEcd, comPolys = enc.round(w, rand, wEcd)                  # RandEncode of rows sel, Coeffs[:rank+1] contiguous
+
+and the MustSetRandom draws all of these take, made on the device (element.go:299-343):
+
+    smp = FieldSampler(F, seed)                                # NewUniformSamplerWithSeed(seed) for crypto/rand
+    rand = smp.elems(first, n)                                 # element i: SetRandom from instance first + i
+    masks, maskComs, maskSums = SumCheckMaskBatchSampled(smp, rank, maskRank, embRank, nProofs, first)
 """
 import ctypes
 
@@ -858,6 +864,69 @@ def sumcheck_mask_batch_dev(field, rank, maskRank, embRank, n_proofs, d_rand, d_
         field.h, rank, maskRank, embRank, n, _addr(d_rand, n * maskRank * L), _addr(d_mask, n * embRank * L),
         _addr(d_mask_com, n * maskRank * L) if d_mask_com is not None else None, _addr(d_mask_sum, n * L),
         _stream(stream)))
+
+
+# ---- the prover's MustSetRandom draws on the device (element.go:299-343) ---------------------------
+class FieldSampler:
+    """rg_fsampler: NewUniformSamplerWithSeed(seed) in place of crypto/rand on any built field.  Element i
+    of a call is Uint.SetRandom reading from instance first + i of that sampler; the limbs are the
+    accepted candidate's words as they stand (no domain conversion, as in the reference).  A prover
+    gives each consumer of draws its own seed or a disjoint range of instances."""
+
+    def __init__(self, field, seed):
+        self.field = field
+        seed = bytes(seed)
+        h = vp()
+        _status(lib().rg_field_sampler_create(field.h, seed, len(seed), ctypes.byref(h)))
+        self.h = h
+        self._L = lib()
+
+    def __del__(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None):
+            self._L.rg_field_sampler_destroy(self.h)
+            self.h = None
+
+    def scratch_bytes(self):
+        return lib().rg_field_sampler_scratch_bytes(self.h)
+
+    def elems_dev(self, first, n, d_out, d_scratch, stream=None):
+        """rg_field_sampler_elems_dev: d_out [n][L] <- the elements of instances first .. first + n - 1;
+        d_scratch: scratch_bytes() bytes.  Asynchronous on `stream`."""
+        _status(lib().rg_field_sampler_elems_dev(self.h, first, n, _addr(d_out, n * self.field.L),
+                                                 _addr(d_scratch, self.scratch_bytes() // 8), _stream(stream)))
+
+    def elems(self, first, n):
+        """rg_field_sampler_elems (synchronous) -> [n][L] uint64."""
+        out = np.zeros((max(n, 1), self.field.L), np.uint64)
+        _status(lib().rg_field_sampler_elems(self.h, first, n, ptr(out)))
+        return out[:n]
+
+
+def SumCheckMaskBatchSampled(sampler, rank, maskRank, embRank, n_proofs, first):
+    """Prover.sumCheckMask(maskRank) (prover.go:381-397) of n_proofs proofs whose draw k of proof p is
+    the element of instance first + p * maskRank + k of `sampler`.  Returns (mask [n][embRank][L],
+    maskCom [n][maskRank][L] = mask.Coeffs[:maskRank], maskSum [n][L])."""
+    L, n = sampler.field.L, n_proofs
+    if maskRank > embRank:
+        raise RingoPanic("index out of range")
+    mask = np.zeros((max(n, 1), embRank, L), np.uint64)
+    com = np.zeros((max(n, 1), maskRank, L), np.uint64)
+    msum = np.zeros((max(n, 1), L), np.uint64)
+    _status(lib().rg_buckler_sumcheck_mask_batch_sampled(sampler.h, rank, maskRank, embRank, n, first, ptr(mask),
+                                                         ptr(com), ptr(msum)))
+    return mask[:n], com[:n], msum[:n]
+
+
+def sumcheck_mask_batch_sampled_dev(sampler, rank, maskRank, embRank, n_proofs, first, d_mask, d_mask_sum, d_scratch,
+                                    d_mask_com=None, stream=None):
+    """rg_buckler_sumcheck_mask_batch_sampled_dev: the draws of instances first .. first + n * maskRank - 1
+    -> d_mask [n][embRank][L], d_mask_sum [n][L] and, when given, d_mask_com [n][maskRank][L]; d_scratch:
+    sampler.scratch_bytes() bytes."""
+    L, n = sampler.field.L, n_proofs
+    _status(lib().rg_buckler_sumcheck_mask_batch_sampled_dev(
+        sampler.h, rank, maskRank, embRank, n, first, _addr(d_mask, n * embRank * L),
+        _addr(d_mask_com, n * maskRank * L) if d_mask_com is not None else None, _addr(d_mask_sum, n * L),
+        _addr(d_scratch, sampler.scratch_bytes() // 8), _stream(stream)))
 
 
 # ---- norm decomposition (buckler/utils.go:34-56, buckler/prover.go:77-111, 182-192) ---------------
