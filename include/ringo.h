@@ -88,6 +88,10 @@ rg_status rg_ntt_create_from_tables(const rg_field* f, int rank, int negacyclic,
                                     const uint64_t* tw_inv, const uint64_t* rank_inv, rg_ntt** out);
 void rg_ntt_destroy(rg_ntt* t);
 int rg_ntt_rank(const rg_ntt* t); /* Rank() (ntt.go:139,469) */
+/* Which kernel family serves this plan in one direction, and in how many passes (0 for "stages": one
+ * launch per stage).  name is "stages", "tiled", "lazy64", "fast256", "wide".  Reads the plan only. */
+const char* rg_ntt_route_name(const rg_ntt* t, int inverse);
+int rg_ntt_passes(const rg_ntt* t, int inverse);
 /* Copy the tables out (Montgomery, [rank][L] each + one element). */
 rg_status rg_ntt_tables(const rg_ntt* t, uint64_t* tw, uint64_t* tw_inv, uint64_t* rank_inv);
 

@@ -27,7 +27,8 @@ void set_last_error(const std::string& msg);
 // read when a plan is created (ntt.hip finalize()) and hold for the plan's life; the probe is read
 // by every call.
 enum class Knob : int {
-  NttKernel,   // RINGO_NTT_KERNEL   r*: generic single-word / q255 pass kernels; stage: wide fields per stage
+  NttKernel,   // RINGO_NTT_KERNEL   r*: generic single-word / q255 pass kernels; stage: wide fields per stage;
+               //                    w3: wide fields in three passes from 2^3 up (ntt_route.hpp ntt_wide_long)
   NttChunkMb,  // RINGO_NTT_CHUNK_MB polys per pass pair bounded to this many MiB
   JindoMac,    // RINGO_JINDO_MAC    l: mac_kernel instead of the MFMA MAC
   JindoSplit,  // RINGO_JINDO_SPLIT  0: commit_sampled on the caller's stream only

@@ -247,8 +247,20 @@ static rg_status finalize(rg_ntt* t) {
   H.inverse(ninv, n);
   const bool halving = H.eq(ninv, &t->h_ninv[0]);
   const char* sw = knob(Knob::NttKernel);
-  const NttRouting r[2] = {ntt_route(L, t->f.q, t->logN, false, halving, sw),
-                           ntt_route(L, t->f.q, t->logN, true, halving, sw)};
+  NttRouting r[2] = {ntt_route(L, t->f.q, t->logN, false, halving, sw),
+                     ntt_route(L, t->f.q, t->logN, true, halving, sw)};
+  // the wide fields' passes: ntt_route()'s one or two, or above 2^16 (where it answers Stages; and
+  // under the experiments build's w3 switch) the up to three of the long route
+  WidePasses wp[2];
+  for (int d = 0; d < 2; ++d) {
+    wp[d] = ntt_wide_long(L, t->f.q, t->logN, d == 1, halving, sw);
+    if (wp[d].npasses) {
+      r[d].route = NttRoute::Wide;
+      r[d].npasses = 0;
+    } else if (r[d].route == NttRoute::Wide) {
+      wp[d] = {r[d].npasses, {r[d].passes[0], r[d].passes[1], {0, 0}}};
+    }
+  }
   const uint64_t* twi1 = N >= 2 ? &t->h_twinv[(size_t)1 * L] : H.one;
   memcpy(t->nsc, &t->h_ninv[0], 8 * L);
   H.mul(t->w1n, twi1, &t->h_ninv[0]);  // twInv[1] * N^-1 for the fused last inverse stage
@@ -272,6 +284,7 @@ static rg_status finalize(rg_ntt* t) {
     p.logN = t->logN;
     p.chunk_polys = chunk_polys(r[d], (size_t)N * L * 8);
     p.tile16 = ntt64_tile16(r[d].mont, sw);
+    p.wide = wp[d];
     p.aux = t->aux.get();
   }
   return RG_OK;
@@ -367,6 +380,22 @@ rg_status rg_ntt_create_from_tables(const rg_field* f, int rank, int negacyclic,
 void rg_ntt_destroy(rg_ntt* t) { delete t; }
 int rg_ntt_rank(const rg_ntt* t) { return t ? t->N : 0; }
 
+const char* rg_ntt_route_name(const rg_ntt* t, int inverse) {
+  if (!t) return nullptr;
+  switch (t->dir[inverse != 0].route) {
+    case NttRoute::Tiled: return "tiled";
+    case NttRoute::Lazy64: return "lazy64";
+    case NttRoute::Fast256: return "fast256";
+    case NttRoute::Wide: return "wide";
+    default: return "stages";
+  }
+}
+
+int rg_ntt_passes(const rg_ntt* t, int inverse) {
+  if (!t) return -1;
+  const NttLaunch& p = t->dir[inverse != 0];
+  return p.route == NttRoute::Wide ? p.wide.npasses : p.npasses;
+}
 
 rg_status rg_ntt_tables(const rg_ntt* t, uint64_t* tw, uint64_t* tw_inv, uint64_t* rank_inv) {
   if (!t) return RG_ERR_INVALID;

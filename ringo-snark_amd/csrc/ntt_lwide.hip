@@ -1,7 +1,8 @@
 // ntt_lwide.hip -- wide buckler fields (zp440: 7 limbs, zp880: 14 limbs): the Wide route's runner
-// (the LDS-tiled pass kernel of ntt_wide.hpp over the plan's passes: COL then ROW, one pass for
-// N <= 2^8) and the Stages route's per-stage kernels of ntt_kernels.hpp.  ntt_route.hpp decides
-// per direction which of the two a plan takes; this unit derives WideArgs from the modulus.
+// (the LDS-tiled pass kernel of ntt_wide.hpp over the plan's passes: one pass for N <= 2^8, COL
+// then ROW up to 2^16, three passes on the long route up to 2^24) and the Stages route's per-stage
+// kernels of ntt_kernels.hpp.  ntt_route.hpp decides per direction which of the two a plan takes
+// and in which passes; this unit derives WideArgs from the modulus.
 #include "ntt_kernels.hpp"
 #include "ntt_wide.hpp"
 
@@ -10,7 +11,19 @@ namespace rg {
 template <int L>
 static rg_status wide_run(const NttLaunch& p, hipStream_t st) {
   if (p.route != NttRoute::Wide) return run_stages<L, false>(p, st);
-  const int logN = p.logN;
+  const int logN = p.logN, np = p.wide.npasses;
+  // every pass's grid, before anything is launched: `grid` goes to the launch as an unsigned
+  long long grids[3];
+  for (int k = 0; k < np; ++k) {
+    const PassDesc& ps = p.wide.passes[k];
+    grids[k] = wide_grid(p.batch, logN, ps.P, wide_cpt(ps.P, logN - ps.G0 - ps.P));
+    if (grids[k] < 0) {
+      set_last_error("rg_ntt: batch " + std::to_string(p.batch) + " at rank 2^" + std::to_string(logN) + " needs more than " +
+                     std::to_string(kWideMaxGrid) + " workgroups in the pass of " + std::to_string(ps.P) +
+                     " stages: split the batch");
+      return RG_ERR_INVALID;
+    }
+  }
   WideArgs a;
   memset(&a, 0, sizeof(a));
   a.tw = p.tw;  // inverse: twInv[i] / 2 (ntt.hip upload_wide)
@@ -26,23 +39,21 @@ static rg_status wide_run(const NttLaunch& p, hipStream_t st) {
     a.q28[k] = (uint32_t)v & 0x0FFFFFFFu;
   }
   a.logN = logN;
-  const int base_cpt = 1;  // one 256-point sub-transform per workgroup at P = 8: 14 / 28 KiB of LDS, so LDS does not cap occupancy below the VGPRs
-  for (int k = 0; k < p.npasses; ++k) {
-    const PassDesc& ps = p.inv ? p.passes[p.npasses - 1 - k] : p.passes[k];
+  for (int k = 0; k < np; ++k) {
+    const int at = p.inv ? np - 1 - k : k;  // the inverse runs the passes backwards
+    const PassDesc& ps = p.wide.passes[at];
     a.G0 = ps.G0;
     a.P = ps.P;
     a.logS = logN - a.G0 - a.P;
-    a.cpt = std::max(base_cpt, 256 >> a.P);
-    if (a.logS > 0) a.cpt = std::min(a.cpt, 1 << a.logS);  // a COL tile stays inside one row of columns
+    a.cpt = wide_cpt(a.P, a.logS);  // one 256-point tile per workgroup, inside one row of columns
     a.nsub = (long long)p.batch << (logN - a.P);
     a.in = k == 0 ? p.in : p.out;
     a.out = p.out;
     const size_t lds = (size_t)a.cpt * ((size_t)1 << a.P) * L * 8;
-    const long long grid = (a.nsub + a.cpt - 1) / a.cpt;
     if (p.inv)
-      hipLaunchKernelGGL((ntt_wide_pass<L, true>), dim3((unsigned)grid), dim3(kWideThreads), lds, st, a);
+      hipLaunchKernelGGL((ntt_wide_pass<L, true>), dim3((unsigned)grids[at]), dim3(kWideThreads), lds, st, a);
     else
-      hipLaunchKernelGGL((ntt_wide_pass<L, false>), dim3((unsigned)grid), dim3(kWideThreads), lds, st, a);
+      hipLaunchKernelGGL((ntt_wide_pass<L, false>), dim3((unsigned)grids[at]), dim3(kWideThreads), lds, st, a);
     RG_TRY(check_launch("ntt_wide_pass"));
   }
   return RG_OK;

@@ -26,6 +26,8 @@ struct NttLaunch : NttRouting {  // the direction's route, table format and pass
   int logN;
   size_t chunk_polys;  // Tiled (two passes), Lazy64: polynomials per pass pair
   bool tile16;         // Lazy64: ROW forward (RP) / COL inverse on 16 points per thread (ntt_route.hpp)
+  WidePasses wide;     // Wide: the passes ntt_wide_pass runs, up to three (ntt_route()'s one or two, or
+                       // ntt_wide_long()'s: then NttRouting's own list, which holds two, stays empty)
   struct Aux* aux;  // Fast256: the plan's helper stream for the two-half split; else null
 };
 

@@ -1,7 +1,8 @@
 // ntt_route.hpp -- which of the five NTT kernel families serves a plan, and in which passes:
-// decided once, when the plan is created (ntt.hip finalize()), by ntt_route() below.  HIP-free,
-// <stdint.h> only: tests/test_ntt_route_host.py compiles it with g++ and walks every field, rank,
-// direction and switch value.  DESIGN.md section 4.0 has the rules as a table.
+// decided once, when the plan is created (ntt.hip finalize()), by ntt_route() below and, for the
+// wide fields above 2^16, by ntt_wide_long() at the end.  HIP-free, <stdint.h> only:
+// tests/test_ntt_route_host.py and tests/test_ntt_wide_long_host.py compile it with g++ and walk
+// every field, rank, direction and switch value.  DESIGN.md section 4.0 has the rules as a table.
 #pragma once
 #include <stdint.h>
 
@@ -38,7 +39,8 @@ enum class NttRoute : int {
   Tiled,    // ntt_pass_kernel / ntt_r2 / ntt_r8, LDS-tiled: L <= 4, kMinTiledP <= logN <= 2 pmax
   Lazy64,   // ntt16_pass (ntt64.hpp): L = 1, q < 2^63, q mod 2^32 == 1, logN = 16
   Fast256,  // ntt256_pass (ntt256.hpp): L = 4, q[0] == 1, q < 2^255, logN = 15, 16
-  Wide      // ntt_wide_pass (ntt_wide.hpp): L = 7, 14, spare top bit, 1 <= logN <= 16
+  Wide      // ntt_wide_pass (ntt_wide.hpp): L = 7, 14, spare top bit, 1 <= logN <= 16 here;
+            // 17 <= logN <= 24 by ntt_wide_long() below
 };
 
 // a pass covers the P global stages [G0, G0 + P)
@@ -88,6 +90,49 @@ inline NttRouting ntt_route(int L, const uint64_t* q, int logN, bool inv, bool h
   const int half = logN / 2 < kMinTiledP ? kMinTiledP : logN / 2;
   ntt_set_passes(r, logN, logN <= ntt_pmax(L) ? logN : half);
   return r;
+}
+
+// ---- the long wide route: ntt_wide_pass in up to three passes, 2^17 <= N <= 2^24 ----
+// Buckler's evaluator and encoder run at embRank = 4 rank under any infinity-norm constraint with
+// bound >= 1 (w w w - w has maxRank 3 rank + 1), so the reference's LogN = 15 benchmark
+// transforms at 2^17.  ntt_route() above keeps its answer there (Stages, no passes: its pass list
+// holds two); finalize() asks ntt_wide_long() for every L = 7, 14 plan and, where it gives
+// passes, runs the direction on ntt_wide_pass over them instead.
+constexpr int kWidePassStages = 8;  // most stages of one ntt_wide_pass launch (a 256-point tile)
+constexpr int kWideLongMin = 17, kWideLongMax = 24;
+constexpr int kWideForcedMin = 3;   // the w3 switch: three passes need three stages
+
+struct WidePasses {
+  int npasses;  // 0: no long route for this plan and direction
+  PassDesc passes[3];  // forward order, contiguous from G0 = 0
+};
+
+// logN stages in n passes, as evenly as possible, larger passes first
+inline WidePasses ntt_wide_split(int logN, int n) {
+  WidePasses w = {n, {{0, 0}, {0, 0}, {0, 0}}};
+  for (int k = 0, g0 = 0; k < n; ++k) {
+    const int P = logN / n + (k < logN % n ? 1 : 0);
+    w.passes[k] = {g0, P};
+    g0 += P;
+  }
+  return w;
+}
+
+// Same arguments as ntt_route().  L = 7, 14 with 17 <= logN <= 24, the top bit of q clear, not
+// (inverse and rank_inv != N^-1: the inverse scales by halving every stage) and a switch that
+// does not start with s: ceil(logN / 8) passes (always three here: 17 -> 6, 6, 5; 20 -> 7, 7, 6;
+// 24 -> 8, 8, 8).  Three passes of <= 8 and not two of 9: the transform is bound by the
+// multiplier, a third HBM round trip costs a few percent, a 512-point L = 14 tile doubles the LDS
+// per workgroup.  The switch w3 (experiments build) forces three even passes onto any
+// 3 <= logN <= 24 under the same conditions, so the middle pass runs at sizes a test can afford.
+inline WidePasses ntt_wide_long(int L, const uint64_t* q, int logN, bool inv, bool halving, const char* sw) {
+  const WidePasses none = {0, {{0, 0}, {0, 0}, {0, 0}}};
+  if (L != 7 && L != 14) return none;
+  const bool per_stage = sw && sw[0] == 's', forced = sw && sw[0] == 'w' && sw[1] == '3';
+  if ((q[L - 1] >> 63) != 0 || (inv && !halving) || per_stage) return none;
+  if (forced && logN >= kWideForcedMin && logN <= kWideLongMax) return ntt_wide_split(logN, 3);
+  if (logN < kWideLongMin || logN > kWideLongMax) return none;
+  return ntt_wide_split(logN, (logN + kWidePassStages - 1) / kWidePassStages);
 }
 
 }  // namespace rg

@@ -6,17 +6,23 @@
 // ~0.5 G wave-lane multiplies against 7.3 MB of data.  What the one-launch-per-stage kernel
 // (ntt_stage_kernel) wasted was 16 HBM round trips per transform plus a 64-bit-limb CIOS with
 // explicit compare-based carries.  Here:
-//   * passes of P <= 8 stages (N = 2^16: COL 8 + ROW 8, N = 2^15: 7 + 8, N <= 2^8: one pass):
-//     a workgroup loads `cpt` sub-transforms (2^P points at stride S) into limb-planar LDS, runs
-//     the P radix-2 stages with one butterfly per thread per step and a barrier between stages,
-//     and writes the tile back -- HBM sees one read and one write per element per pass;
+//   * passes of P <= 8 stages (N <= 2^8: one pass; up to 2^16 two, COL then ROW: 2^16 is 8 + 8,
+//     2^15 is 7 + 8; 2^17 .. 2^24, the long route, three: 2^17 is 6 + 6 + 5, 2^24 is 8 + 8 + 8 --
+//     Buckler's embedding rank is 4 x the witness rank under any norm constraint, so LogN = 15
+//     transforms at 2^17): a workgroup loads `cpt` sub-transforms (2^P points at stride S) into
+//     limb-planar LDS, runs the P radix-2 stages with one butterfly per thread per step and a
+//     barrier between stages, and writes the tile back -- HBM sees one read and one write per
+//     element per pass.  The pass position (G0, P, logS) is an argument: the middle pass of the
+//     long route (G0 > 0 and logS > 0) is the same kernel, its index algebra is
+//     ntt_wide_tile.hpp, which tests/test_ntt_wide_long_host.py replays on the host;
 //   * the product is Montgomery on 28-bit digits (mont28), product scanning with one 64-bit column
 //     accumulator: one v_mad_u64_u32 per partial product and no carry handling (the round-4
 //     32-bit-digit form, a v_mad_u64_u32 plus a v_addc per product, is
 //     tools/experiments/wide_mont32.patch);
 //   * every value stays canonical in [0, q) (one conditional subtract per add / sub / product:
 //     ~3 D operations against ~4 D^2 for the product), so limbs equal the reference's.
-// Twiddles are the reference's Montgomery tables tw[m + i] / twInv[m + i], read from L2.  The
+// Twiddles are the reference's Montgomery tables tw[m + i] / twInv[m + i], read through L2 (a
+// 2^17-entry table is 7.3 / 14.7 MB at L = 7 / 14, past the 4 MB L2: DESIGN.md 4.2b).  The
 // inverse halves every stage ((u + v) / 2, (u - v) twInv[m + i] / 2 from a halved copy of the
 // table) instead of multiplying by N^-1 after the last one: log N halvings are N^-1, a halving is
 // ~3 D operations, and the butterfly keeps ONE product site (a second one for the N^-1 factor
@@ -28,6 +34,7 @@
 
 #include "common.hpp"
 #include "ntt64.hpp"
+#include "ntt_wide_tile.hpp"
 
 namespace rg {
 
@@ -180,7 +187,6 @@ __global__ __launch_bounds__(kWideThreads, 2) void ntt_wide_pass(WideArgs a) {  
   const int P = a.P, NP = 1 << P, cpt = a.cpt, logS = a.logS;
   const int plane = cpt * NP;
   const long long s0 = (long long)blockIdx.x * cpt;
-  const int subs_log = a.logN - P;  // log2 sub-transforms per polynomial
   uint32_t q[D];
 #pragma unroll
   for (int i = 0; i < D; ++i) q[i] = a.q[i];
@@ -188,18 +194,12 @@ __global__ __launch_bounds__(kWideThreads, 2) void ntt_wide_pass(WideArgs a) {  
     mont28<L>(z, x, y, q, a.q28, a.qinv28);
   };
   // global element index of point x of tile sub-transform c (or -1 past the batch)
-  auto elem = [&](int c, int x) -> long long {
-    const long long s = s0 + c;
-    if (s >= a.nsub) return -1;
-    const long long b = s >> subs_log, r = s & ((1LL << subs_log) - 1);
-    const long long hi = r >> logS, lo = r & ((1LL << logS) - 1);
-    return (b << a.logN) | (hi << (a.logN - a.G0)) | ((long long)x << logS) | lo;
-  };
+  auto elem = [&](int c, int x) -> long long { return wide_elem(s0 + c, a.nsub, a.logN, a.G0, P, logS, x); };
   // ---- HBM -> LDS: memory-friendly order (rows: c, x, l; columns: x, c, l)
   const int W = cpt * NP * L;
   for (int f = threadIdx.x; f < W; f += kWideThreads) {
     const int l = f % L, e = f / L;
-    const int c = logS == 0 ? e / NP : e % cpt, x = logS == 0 ? e % NP : e / cpt;
+    const int c = wide_load_c(P, logS, cpt, e), x = wide_load_x(P, logS, cpt, e);
     const long long g = elem(c, x);
     if (g >= 0) lds[l * plane + c * NP + x] = a.in[g * L + l];
   }
@@ -208,11 +208,8 @@ __global__ __launch_bounds__(kWideThreads, 2) void ntt_wide_pass(WideArgs a) {  
   const int nbf = cpt * (NP >> 1);
   // twiddle index of butterfly bf at local stage g
   auto tw_idx = [&](int g, int bf) -> long long {
-    const int c = bf >> (P - 1), p = bf & ((NP >> 1) - 1), bitpos = P - 1 - g;
-    const int x0 = ((p >> bitpos) << (bitpos + 1)) | (p & ((1 << bitpos) - 1));
-    const long long r = (s0 + c) & ((1LL << subs_log) - 1);
-    const long long hi = (r >> logS) & ((1LL << a.G0) - 1);
-    return (1LL << (a.G0 + g)) + (hi << g) + (x0 >> (bitpos + 1));
+    const int c = bf >> (P - 1), p = bf & ((NP >> 1) - 1);
+    return wide_tw_idx(s0 + c, a.logN, a.G0, P, logS, g, wide_bfly_x0(P, g, p));
   };
   // L = 14: the next butterfly's twiddle is loaded one butterfly ahead (across the stage barrier),
   // so its L2 latency hides behind the current product, which 2 waves/SIMD do not (zp880 +1.3%);
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(kWideThreads, 2) void ntt_wide_pass(WideArgs a) {  
     const int bitpos = P - 1 - g;
     for (int bf = threadIdx.x; bf < nbf; bf += kWideThreads) {
       const int c = bf >> (P - 1), p = bf & ((NP >> 1) - 1);
-      const int x0 = ((p >> bitpos) << (bitpos + 1)) | (p & ((1 << bitpos) - 1)), x1 = x0 | (1 << bitpos);
+      const int x0 = wide_bfly_x0(P, g, p), x1 = x0 | (1 << bitpos);
       uint32_t u[D], v[D], w[D];
 #pragma unroll
       for (int l = 0; l < L; ++l) {
@@ -295,7 +292,7 @@ __global__ __launch_bounds__(kWideThreads, 2) void ntt_wide_pass(WideArgs a) {  
   // ---- LDS -> HBM
   for (int f = threadIdx.x; f < W; f += kWideThreads) {
     const int l = f % L, e = f / L;
-    const int c = logS == 0 ? e / NP : e % cpt, x = logS == 0 ? e % NP : e / cpt;
+    const int c = wide_load_c(P, logS, cpt, e), x = wide_load_x(P, logS, cpt, e);
     const long long g = elem(c, x);
     if (g >= 0) a.out[g * L + l] = lds[l * plane + c * NP + x];
   }

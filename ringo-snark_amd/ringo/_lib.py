@@ -65,6 +65,8 @@ _SIGS = {
                                                  ctypes.POINTER(vp)]),
     "rg_ntt_destroy": (None, [vp]),
     "rg_ntt_rank": (ctypes.c_int, [vp]),
+    "rg_ntt_route_name": (ctypes.c_char_p, [vp, ctypes.c_int]),
+    "rg_ntt_passes": (ctypes.c_int, [vp, ctypes.c_int]),
     "rg_ntt_tables": (ctypes.c_int, [vp, u64p, u64p, u64p]),
     "rg_ntt_fwd": (ctypes.c_int, [vp, u64p, u64p, ctypes.c_size_t]),
     "rg_ntt_fwd_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp]),

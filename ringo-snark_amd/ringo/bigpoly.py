@@ -142,6 +142,12 @@ class _Transformer:
     def Rank(self):
         return self.rank
 
+    def route(self, inverse=False):
+        """(name, passes) of the kernel family that serves this plan in one direction: "stages" (0 passes:
+        one launch per stage), "tiled", "lazy64", "fast256" or "wide" (rg_ntt_route_name, rg_ntt_passes)."""
+        name = lib().rg_ntt_route_name(self.h, 1 if inverse else 0)
+        return name.decode(), lib().rg_ntt_passes(self.h, 1 if inverse else 0)
+
     def tables(self):
         L = self.field.L
         tw = np.zeros((self.rank, L), np.uint64)

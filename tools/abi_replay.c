@@ -301,6 +301,9 @@ static int mode_refuse(void) {
   EXPECT(RG_ERR_INVALID, rg_set_probe(1)); /* the product library has no measurement switch */
   EXPECT(RG_OK, rg_set_probe(0));
   if (rg_jindo_scratch_bytes(NULL, 3) != 0) fail("rg_jindo_scratch_bytes(NULL, 3) != 0", 1, 0);
+  /* the plan's route report: no plan, no route (checked, not printed) */
+  if (rg_ntt_route_name(NULL, 0) != NULL || rg_ntt_route_name(NULL, 1) != NULL) fail("rg_ntt_route_name(NULL) != NULL", 1, 0);
+  if (rg_ntt_passes(NULL, 0) != -1 || rg_ntt_passes(NULL, 1) != -1) fail("rg_ntt_passes(NULL) != -1", 1, 0);
   /* the Buckler verifier's entries: checked, not printed (the lines above are read as a fixed set) */
   {
     rg_bverifier* v = NULL;
