@@ -88,16 +88,19 @@ rg_status rg_ntt_create_from_tables(const rg_field* f, int rank, int negacyclic,
                                     const uint64_t* tw_inv, const uint64_t* rank_inv, rg_ntt** out);
 void rg_ntt_destroy(rg_ntt* t);
 int rg_ntt_rank(const rg_ntt* t); /* Rank() (ntt.go:139,469) */
-/* Which kernel family serves this plan in one direction, and in how many passes (0 for "stages": one
- * launch per stage).  name is "stages", "tiled", "lazy64", "fast256", "wide".  Reads the plan only. */
+/* Which kernel family serves this plan in one direction, and in how many passes.  name is "stages" (0
+ * passes: one launch per stage), "tiled" (1 or 2), "lazy64" (2), "fast256" (2 at rank 2^15 / 2^16, 3 at
+ * 2^17 .. 2^19), "wide" (1 or 2 up to rank 2^16, 3 at 2^17 .. 2^24).  Reads the plan only. */
 const char* rg_ntt_route_name(const rg_ntt* t, int inverse);
 int rg_ntt_passes(const rg_ntt* t, int inverse);
 /* Copy the tables out (Montgomery, [rank][L] each + one element). */
 rg_status rg_ntt_tables(const rg_ntt* t, uint64_t* tw, uint64_t* tw_inv, uint64_t* rank_inv);
 
 /* FwdNTTTo(vOut, v) (ntt.go:98-115,206-223) on `batch` polys: natural -> bit-reversed.
- * The _dev forms order all their work on `stream`; a 4-limb plan at rank 2^15 / 2^16 runs half of a
- * batch of 8+ on a helper stream of its own, forked from and joined back into `stream`. */
+ * The _dev forms order all their work on `stream`; a "fast256" plan (4 limbs, q = 1 mod 2^64, q < 2^255)
+ * runs half of its work on a helper stream of its own, forked from and joined back into `stream`: at
+ * rank 2^15 / 2^16 from a batch of 8 up, at rank 2^17 .. 2^19 from 8 blocks of 2^16 points up (batch
+ * 4, 2, 1). */
 rg_status rg_ntt_fwd(const rg_ntt* t, uint64_t* out, const uint64_t* in, size_t batch);
 rg_status rg_ntt_fwd_dev(const rg_ntt* t, uint64_t* d_out, const uint64_t* d_in, size_t batch, void* stream);
 /* InvNTTTo(vOut, v) (ntt.go:118-136,226-244): bit-reversed -> natural, times rank^-1. */

@@ -24,7 +24,7 @@ struct rg_ntt {
   rg::DevBuf d_tw, d_twinv;                     // the format the plan's routes read (finalize)
   uint64_t nsc[16], nsc_sh, w1n[16], w1n_sh;    // rank_inv and twInv[1] rank_inv in that format
   rg::NttLaunch dir[2];          // forward, inverse: all of a launch but in, out and batch
-  std::unique_ptr<rg::Aux> aux;  // Fast256: helper stream of ntt256_run's split (ntt_l4_fast.hip)
+  std::unique_ptr<rg::Aux> aux;  // Fast256 (either direction): helper stream of ntt256_run's split (ntt_l4_fast.hip)
   int device = 0;                // the tables and the helper stream live on this device
 };
 
@@ -261,6 +261,14 @@ static rg_status finalize(rg_ntt* t) {
       wp[d] = {r[d].npasses, {r[d].passes[0], r[d].passes[1], {0, 0}}};
     }
   }
+  // the 4-limb q = 1 mod 2^64 plans at 2^17 .. 2^19 (where ntt_route() answers Tiled): Fast256 in
+  // three passes, which ntt256_run derives from logN; NttRouting's own list, which holds two, is unused
+  for (int d = 0; d < 2; ++d)
+    if (ntt_fast256_long(L, t->f.q, t->logN, d == 1, halving, sw)) {
+      r[d].route = NttRoute::Fast256;
+      r[d].npasses = 3;
+      r[d].passes[0] = r[d].passes[1] = {0, 0};
+    }
   const uint64_t* twi1 = N >= 2 ? &t->h_twinv[(size_t)1 * L] : H.one;
   memcpy(t->nsc, &t->h_ninv[0], 8 * L);
   H.mul(t->w1n, twi1, &t->h_ninv[0]);  // twInv[1] * N^-1 for the fused last inverse stage
@@ -269,7 +277,8 @@ static rg_status finalize(rg_ntt* t) {
   else if (r[0].shoup) RG_TRY(upload_shoup(t, r[0].route == NttRoute::Lazy64));
   else if (r[1].route == NttRoute::Wide) RG_TRY(upload_wide(t));
   else RG_TRY(upload_plain(t));
-  if (r[0].route == NttRoute::Fast256) RG_TRY(create_helper_stream(t));
+  // (a plan with one direction long and the other Tiled: both read upload_plain's tables)
+  if (r[0].route == NttRoute::Fast256 || r[1].route == NttRoute::Fast256) RG_TRY(create_helper_stream(t));
   for (int d = 0; d < 2; ++d) {
     NttLaunch& p = t->dir[d];  // in, out, batch: run()
     static_cast<NttRouting&>(p) = r[d];

@@ -14,6 +14,8 @@
 // Structure as ntt16_pass (ntt64.hpp): two 8-stage passes (COL, ROW), one tile per workgroup,
 // here 4 sub-transforms x 256 points (32 KiB) per 128-thread workgroup, 8 points per thread,
 // rounds of 3 + 3 + 2 stages through limb-planar LDS images.
+// N = 2^17 .. 2^19 (ntt_route.hpp ntt_fast256_long): the same two passes over the 2^16-point blocks
+// of the polynomial, and ntt256_edge_pass at the end of this file for the 1 to 3 stages above them.
 #pragma once
 #include <stdint.h>
 
@@ -27,7 +29,9 @@ struct Ntt256Args {
   const uint64_t* tw;  // Montgomery twiddles [N][4]
   uint32_t q[8], q2[8];
   uint32_t w1n[8];           // twInv[1] N^-1, Montgomery
-  long long total_sub;       // batch * 256
+  long long total_sub;       // batch * 256; ntt256_edge_pass: its threads, batch * 2^16
+  uint32_t blk0;             // N > 2^16: this launch's first 2^16 block, counted over the whole batch
+                             // (the second half of the split); last, so the fields above keep their place
 };
 
 #if defined(__HIPCC__)
@@ -161,9 +165,11 @@ RG_NTT256_BFLY D16 bfly_inv256(D8 x, D8 y, D8 w, const Ntt256Args* a) {
 
 // LOGC: bits of the pass's sub-transform (8: 256 points; 7: the 128-point COL pass of N = 2^15,
 // whose patterns are H x = t + 16 y, M x = (y>>2) 64 + (t>>2) 16 + (y&3) 4 + (t&3), L x = 8 t + r)
-template <int RK, int LO, int PAT, bool INV, bool SCALE, bool COL, int LOGN = 16, int LOGC = 8>
+// LONG: the tile is a 2^16 block of a longer transform (ntt256_pass with LOGNT > 16); boff, uniform
+// over the workgroup, moves every twiddle index to the block's place in that transform's table
+template <int RK, int LO, int PAT, bool INV, bool SCALE, bool COL, int LOGN = 16, int LOGC = 8, bool LONG = false>
 __device__ __forceinline__ void ntt256_round(const Ntt256Args& a, __amdgpu_buffer_rsrc_t twr, uint32_t (&e)[8][8],
-                                             uint32_t hi, uint32_t t, bool rowuni) {
+                                             uint32_t hi, uint32_t t, bool rowuni, uint32_t boff = 0) {
   constexpr int G0 = COL ? 0 : LOGN - 8;
   auto xof = [&](int rho) -> uint32_t {
     if (PAT == 0) return t + (1u << (LOGC - 3)) * rho;
@@ -191,7 +197,8 @@ __device__ __forceinline__ void ntt256_round(const Ntt256Args& a, __amdgpu_buffe
 #pragma unroll
         for (int i = 0; i < 8; ++i) w[i] = a.w1n[i];
       } else {
-        const uint32_t idx = (1u << (G0 + k)) + (hi << k) + (xof(rho0) >> (b + 1));
+        uint32_t idx = (1u << (G0 + k)) + (hi << k) + (xof(rho0) >> (b + 1));
+        if constexpr (LONG) idx = ntt_long_block_tw(idx, boff, G0 + k);
         if ((COL || rowuni) && PAT == 0) {  // wave-uniform index: scalar loads
           const uint32_t iu = __builtin_amdgcn_readfirstlane(idx);
           const uint32_t* p = reinterpret_cast<const uint32_t*>(a.tw) + 8u * iu;
@@ -238,9 +245,20 @@ constexpr int kNtt256Planes = 2;
 // PROBE (experiments build only, rg_set_probe(5); production = 0): 1 = no HBM data movement,
 // the tile synthesised in registers and the result kept live by a store that never fires, so the
 // same launch times the butterflies, twiddle loads and LDS exchanges alone.
-template <bool INV, bool COL, bool SCALE, bool CANON, bool RP, int LOGN = 16, int PROBE = 0>
+// LOGNT = 17, 18, 19 (ntt_route.hpp ntt_fast256_long; M = LOGNT - 16): the same COL / ROW pass over
+// the batch 2^M contiguous 2^16-point blocks of the polynomials, every twiddle index moved to the
+// block's place in the 2^LOGNT-point table.  COL and ROW tiles are both 1024 points, 64 to a block;
+// ROW without RP (four consecutive rows of one block), so the block is uniform over the workgroup.
+// The M stages above the blocks are ntt256_edge_pass's.
+template <bool INV, bool COL, bool SCALE, bool CANON, bool RP, int LOGNT = 16, int PROBE = 0>
 __global__ __launch_bounds__(128) void ntt256_pass(Ntt256Args a) {
-  static_assert(LOGN == 15 || LOGN == 16, "ntt256_pass: N = 2^15 or 2^16");
+  static_assert(LOGNT >= 15 && LOGNT <= 19, "ntt256_pass: N = 2^15 .. 2^19");
+  constexpr bool LONG = LOGNT > 16;
+  constexpr int LOGN = LONG ? 16 : LOGNT;  // the tile's transform: the polynomial, or a block of it
+  static_assert(!LONG || (!RP && !SCALE && PROBE == 0), "ntt256_pass: the long route's blocks are plain passes");
+  uint32_t boff = 0;
+  if constexpr (LONG)
+    boff = ntt_long_block_off(LOGNT - 16, (a.blk0 + (blockIdx.x >> 6)) & ((1u << (LOGNT - 16)) - 1u));
   constexpr int LOGC = COL ? LOGN - 8 : 8;        // bits of a sub-transform
   constexpr uint32_t CPT = COL ? (1024u >> LOGC) : 4u;  // sub-transforms per tile
   constexpr int PITCH = COL ? (LOGC == 8 ? 296 : 148) : 288, PLANE = (int)CPT * PITCH;
@@ -332,11 +350,11 @@ __global__ __launch_bounds__(128) void ntt256_pass(Ntt256Args a) {
   if constexpr (!INV) {
 #pragma unroll
     for (int y = 0; y < 8; ++y) gload(y, xH(y));
-    ntt256_round<3, LOGC - 3, 0, false, false, COL, LOGN, LOGC>(a, twr, e, hi, t, rowuni);
+    ntt256_round<3, LOGC - 3, 0, false, false, COL, LOGN, LOGC, LONG>(a, twr, e, hi, t, rowuni, boff);
     xchg(xH, HM, xM, HM, false);
-    ntt256_round<LOGC - 5, 2, 1, false, false, COL, LOGN, LOGC>(a, twr, e, hi, t, rowuni);
+    ntt256_round<LOGC - 5, 2, 1, false, false, COL, LOGN, LOGC, LONG>(a, twr, e, hi, t, rowuni, boff);
     xchg(xM, ML, xL, ML, true);
-    ntt256_round<2, 0, 2, false, false, COL, LOGN, LOGC>(a, twr, e, hi, t, rowuni);
+    ntt256_round<2, 0, 2, false, false, COL, LOGN, LOGC, LONG>(a, twr, e, hi, t, rowuni, boff);
     if (CANON) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) canon256(e[r], a.q);
@@ -358,17 +376,79 @@ __global__ __launch_bounds__(128) void ntt256_pass(Ntt256Args a) {
       for (int y = 0; y < 8; ++y) gload(y, xH(y));
       xchg(xH, LH, xL, LH, false);
     }
-    ntt256_round<2, 0, 2, true, SCALE, COL, LOGN, LOGC>(a, twr, e, hi, t, rowuni);
+    ntt256_round<2, 0, 2, true, SCALE, COL, LOGN, LOGC, LONG>(a, twr, e, hi, t, rowuni, boff);
     xchg(xL, ML, xM, ML, !COL);
-    ntt256_round<LOGC - 5, 2, 1, true, SCALE, COL, LOGN, LOGC>(a, twr, e, hi, t, rowuni);
+    ntt256_round<LOGC - 5, 2, 1, true, SCALE, COL, LOGN, LOGC, LONG>(a, twr, e, hi, t, rowuni, boff);
     xchg(xM, HM, xH, HM, true);
-    ntt256_round<3, LOGC - 3, 0, true, SCALE, COL, LOGN, LOGC>(a, twr, e, hi, t, rowuni);
+    ntt256_round<3, LOGC - 3, 0, true, SCALE, COL, LOGN, LOGC, LONG>(a, twr, e, hi, t, rowuni, boff);
     if (CANON) {
 #pragma unroll
       for (int y = 0; y < 8; ++y) canon256(e[y], a.q);
     }
 #pragma unroll
     for (int y = 0; y < 8; ++y) gstore(y, xH(y));
+  }
+}
+
+// N = 2^(16 + M), M = 1, 2, 3: the first (forward) or last (inverse) M stages, sub-transforms of
+// 2^M points at element stride 2^16, one per thread, all 2^M elements in registers, no LDS.
+// Neighbouring lanes hold neighbouring offsets, so a wave's loads and stores are 2 KiB runs; the
+// 2^M - 1 twiddles are the same for every thread (scalar loads).  Forward: lazy outputs in [0, 2q) for the COL pass.  Inverse: the
+// last stage is the fused one of the 2^16 route (w1n = twInv[1] N^-1 on the difference, the exact
+// division by 2^(16 + M) on the sum), then the canonical reduction.  total_sub: threads, batch 2^16.
+template <int M, bool INV>
+__global__ __launch_bounds__(256) void ntt256_edge_pass(Ntt256Args a) {
+  static_assert(M >= 1 && M <= 3, "ntt256_edge_pass: 2, 4 or 8 points per thread");
+  constexpr int NP = 1 << M;
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= a.total_sub) return;
+  const size_t pbase = (size_t)(gid >> 16) << (16 + M);  // uniform: 256 divides 2^16
+  const uint32_t o = (uint32_t)gid & 0xffffu;
+  const __amdgpu_buffer_rsrc_t rin = rg_buf(a.in + 4 * pbase);
+  const __amdgpu_buffer_rsrc_t rout = rg_buf(a.out + 4 * pbase);
+  D8 e[NP];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const uint32_t off = (o + ((uint32_t)j << 16)) * 32u;
+    const rg_u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, 0);
+    const rg_u32x4 v1 = __builtin_amdgcn_raw_buffer_load_b128(rin, off + 16u, 0, 0);
+    e[j].d[0] = v0.x; e[j].d[1] = v0.y; e[j].d[2] = v0.z; e[j].d[3] = v0.w;
+    e[j].d[4] = v1.x; e[j].d[5] = v1.y; e[j].d[6] = v1.z; e[j].d[7] = v1.w;
+  }
+#pragma unroll
+  for (int sp = 0; sp < M; ++sp) {
+    const int g = INV ? M - 1 - sp : sp;
+    const int half = 1 << (M - 1 - g);
+    const bool last = INV && g == 0;
+#pragma unroll
+    for (int jj = 0; jj < NP / 2; ++jj) {
+      const int j0 = ((jj >> (M - 1 - g)) << (M - g)) + (jj & (half - 1)), j1 = j0 + half;
+      D8 W;
+      if (last) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) W.d[i] = a.w1n[i];
+      } else {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(a.tw) + 8u * ntt_long_prefix_tw(M, g, (uint32_t)j0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) W.d[i] = p[i];
+      }
+      const D16 R = INV ? bfly_inv256(e[j0], e[j1], W, &a) : bfly_fwd256(e[j0], e[j1], W, &a);
+      e[j0] = R.x;
+      e[j1] = R.y;
+      if constexpr (INV) {
+        if (last) div2p_256<16 + M>(e[j0].d, a.q);  // (u + v) N^-1, N = 2^(16 + M)
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if constexpr (INV) canon256(e[j].d, a.q);
+    const uint32_t off = (o + ((uint32_t)j << 16)) * 32u;
+    rg_u32x4 v0, v1;
+    v0.x = e[j].d[0]; v0.y = e[j].d[1]; v0.z = e[j].d[2]; v0.w = e[j].d[3];
+    v1.x = e[j].d[4]; v1.y = e[j].d[5]; v1.z = e[j].d[6]; v1.w = e[j].d[7];
+    __builtin_amdgcn_raw_buffer_store_b128(v0, rout, off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(v1, rout, off + 16u, 0, 0);
   }
 }
 

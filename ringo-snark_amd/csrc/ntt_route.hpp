@@ -1,8 +1,9 @@
 // ntt_route.hpp -- which of the five NTT kernel families serves a plan, and in which passes:
-// decided once, when the plan is created (ntt.hip finalize()), by ntt_route() below and, for the
-// wide fields above 2^16, by ntt_wide_long() at the end.  HIP-free, <stdint.h> only:
-// tests/test_ntt_route_host.py and tests/test_ntt_wide_long_host.py compile it with g++ and walk
-// every field, rank, direction and switch value.  DESIGN.md section 4.0 has the rules as a table.
+// decided once, when the plan is created (ntt.hip finalize()), by ntt_route() below and, above 2^16,
+// by ntt_wide_long() (the wide fields) and ntt_fast256_long() (the 4-limb q = 1 mod 2^64 fields) at
+// the end.  HIP-free, <stdint.h> only: tests/test_ntt_route_host.py, tests/test_ntt_wide_long_host.py
+// and tests/test_ntt_fast256_long_host.py compile it with g++ and walk every field, rank, direction
+// and switch value.  DESIGN.md section 4.0 has the rules as a table.
 #pragma once
 #include <stdint.h>
 
@@ -38,7 +39,8 @@ enum class NttRoute : int {
   Stages,   // ntt_stage_kernel, one launch per stage: whatever the others leave
   Tiled,    // ntt_pass_kernel / ntt_r2 / ntt_r8, LDS-tiled: L <= 4, kMinTiledP <= logN <= 2 pmax
   Lazy64,   // ntt16_pass (ntt64.hpp): L = 1, q < 2^63, q mod 2^32 == 1, logN = 16
-  Fast256,  // ntt256_pass (ntt256.hpp): L = 4, q[0] == 1, q < 2^255, logN = 15, 16
+  Fast256,  // ntt256_pass (ntt256.hpp): L = 4, q[0] == 1, q < 2^255, logN = 15, 16 here;
+            // 17 <= logN <= 19 by ntt_fast256_long() below
   Wide      // ntt_wide_pass (ntt_wide.hpp): L = 7, 14, spare top bit, 1 <= logN <= 16 here;
             // 17 <= logN <= 24 by ntt_wide_long() below
 };
@@ -134,5 +136,36 @@ inline WidePasses ntt_wide_long(int L, const uint64_t* q, int logN, bool inv, bo
   if (logN < kWideLongMin || logN > kWideLongMax) return none;
   return ntt_wide_split(logN, (logN + kWidePassStages - 1) / kWidePassStages);
 }
+
+// ---- the long Fast256 route: ntt256_pass over 2^16-point blocks plus one register pass ----
+// The 4-limb q = 1 mod 2^64, q < 2^255 plans (q255, zp220) at N = 2^(16 + M), M = 1, 2, 3: Buckler's
+// embedding rank of a LogN = 15 / 16 circuit.  ntt_route() keeps its answer there (Tiled, two
+// passes); finalize() asks ntt_fast256_long() for each direction and, where it says yes, runs the
+// direction as Fast256 in three passes (ntt_l4_fast.hip): forward a prefix of the first M stages
+// with one 2^M-point sub-transform (element stride 2^16) per thread, then the COL and ROW passes
+// of the 2^16 route over the batch 2^M contiguous blocks; inverse ROW, COL, then a suffix of the
+// last M stages whose final stage is the fused one (w1n, exact division by 2^logN): hence not for
+// an inverse whose rank_inv is not N^-1.  A switch that starts with r keeps Tiled, as at 2^16.
+constexpr int kFast256LongMin = 17, kFast256LongMax = 19;
+constexpr int kFast256BlockLog = 16;  // the bottom passes' block: the 2^16 route's polynomial
+
+inline bool ntt_fast256_long(int L, const uint64_t* q, int logN, bool inv, bool halving, const char* sw) {
+  if (L != 4 || q[0] != 1 || (q[3] >> 63) != 0) return false;
+  if (logN < kFast256LongMin || logN > kFast256LongMax) return false;
+  if (inv && !halving) return false;
+  return !(sw && sw[0] == 'r');
+}
+
+// The twiddle indices of the decomposition, in the reference's table layout (stage g of the whole
+// transform reads tw[2^g + i] for its block i, ntt.go:261-275); the kernels call these.
+// Prefix / suffix stage g < M on element j < 2^M of a sub-transform: the butterfly pairs j with
+// j + 2^(M-1-g), and element j lies in block j >> (M - g) of the stage.
+constexpr uint32_t ntt_long_prefix_tw(int M, int g, uint32_t j) { return (1u << g) + (j >> (M - g)); }
+// Bottom passes: stage gl of a 2^16 block is stage M + gl of the transform, and block i of the
+// block's own stage is block (B << gl) + i there, B the block's index in its polynomial:
+// tw[2^(M+gl) + (B << gl) + i] = tw[idx16 + ((2^M - 1 + B) << gl)] for idx16 = 2^gl + i, the index the
+// 2^16 route reads.  ntt_long_block_off() is the per-workgroup constant (0 for M = 0, B = 0).
+constexpr uint32_t ntt_long_block_off(int M, uint32_t B) { return (1u << M) - 1u + B; }
+constexpr uint32_t ntt_long_block_tw(uint32_t idx16, uint32_t boff, int gl) { return idx16 + (boff << gl); }
 
 }  // namespace rg
