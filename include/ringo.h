@@ -128,6 +128,15 @@ rg_status rg_vec(const rg_field* f, int op, uint64_t* out, const uint64_t* a, co
 rg_status rg_vec_dev(const rg_field* f, int op, uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t n,
                      void* stream);
 
+/* Uint.Marshal() (element.go) of n elements: each taken out of Montgomery form and written as 8 * L
+ * big-endian bytes.  Element k is read at d_x + k * x_stride * L words (the strided read of
+ * rg_jindo_eval_point_multi_dev's d_x) and written at d_out + k * out_stride; the bytes between 8 * L
+ * and out_stride are not touched.  Any built field, one launch, asynchronous on `stream`; it exists so
+ * that an evaluation point reaches a device transcript (rg_xof_absorb_plan_dev) without a host copy.
+ * RG_ERR_INVALID: a NULL argument, x_stride of 0, or out_stride < 8 * L with n > 1; n == 0 does nothing. */
+rg_status rg_field_marshal_dev(const rg_field* f, const uint64_t* d_x, size_t n, size_t x_stride, uint8_t* d_out,
+                               size_t out_stride, void* stream);
+
 /* ---- remaining bigpoly operators used by Buckler ------------- */
 /* CyclicEvaluator.QuoRemByVanishing(p, N) (math/bigpoly/cyclic.go:18-37): quotient and
  * remainder of each of `batch` rank-coefficient polynomials by X^n_vanish - 1 (coefficient
@@ -1061,8 +1070,10 @@ rg_status rg_jindo_eval_point_multi_dev(const rg_jindo* j, size_t n_points, cons
  *   d_bq, d_bo     [n_proofs][batch][nq | nqo][d]; both NULL iff batch == 1
  *   d_chals [n_proofs][cols][nq][d]   d_left, d_right, d_scratch  as above
  * The outputs are the d_bq, d_bo, d_chals, d_left and d_right arguments of rg_jindo_verify_multi_dev;
- * a batch verification is: upload the bytes, this call, rg_buckler_verify_checks_multi_dev,
- * rg_jindo_verify_multi_dev, on one stream.  Asynchrony, scratch (the same size:
+ * a batch verification is: the bytes, this call, rg_buckler_verify_checks_multi_dev,
+ * rg_jindo_verify_multi_dev, on one stream.  The bytes are either uploaded from a host transcript or
+ * squeezed in place by a device one (rg_xof_squeeze_dev writes d_batch_bytes and d_chal_bytes in
+ * exactly this layout), in which case nothing of the batch passes through the host.  Asynchrony, scratch (the same size:
  * rg_jindo_verify_inputs_multi_scratch_bytes) and refusals as above, over every output and input; also
  * refused: batch < 1 or above 32768, the NULL rule of d_batch_bytes / d_bq / d_bo, a NULL d_chal_bytes
  * or d_chals, and a ChallengeBound of 0 (rg_jindo_challenge_bound: exp > 120). */
@@ -1073,10 +1084,13 @@ rg_status rg_jindo_verify_inputs_multi_dev(const rg_jindo* j, size_t n_proofs, s
                                            uint64_t* d_right, void* d_scratch, void* stream);
 
 /* Prover.Evaluate (prover.go:205-324) for n_proofs proofs of one handle, in two enqueues around the
- * caller's transcript, which Evaluate reads twice: the batch bytes before openBatch, the challenge
- * bytes after Partial / PartialMask have been absorbed.  A batch is: upload the points and batch
- * bytes, call 1, download d_pf_partial, absorb and squeeze on the host, upload the challenge bytes,
- * call 2 (and rg_poly_evaluate_multi_dev for the evaluations), all on one stream.
+ * transcript, which Evaluate reads twice: the batch bytes before openBatch, the challenge bytes
+ * after Partial / PartialMask have been absorbed.  With a host transcript a batch is: upload the
+ * points and batch bytes, call 1, download d_pf_partial, absorb and squeeze on the host, upload the
+ * challenge bytes, call 2 (and rg_poly_evaluate_multi_dev for the evaluations), all on one stream.
+ * With a device transcript (rg_xof_*, above) there is no host step: rg_xof_squeeze_dev writes
+ * d_batch_bytes before call 1, rg_xof_absorb_plan_dev reads d_pf_partial after it and a second
+ * squeeze writes d_chal_bytes before call 2, one uninterrupted queue.
  *
  * 1. rg_jindo_eval_open_multi_dev (:227-289): the batch challenges' encodings, encode(leftVec(x)),
  *    openBatch and the partials of every proof.
@@ -1131,6 +1145,69 @@ rg_status rg_jindo_eval_respond_multi_dev(const rg_jindo* j, size_t n_proofs, co
                                           const uint64_t* d_ob_mlwe, size_t ob_proof_stride,
                                           const uint8_t* d_chal_bytes, uint64_t* d_pf_enc, uint64_t* d_pf_mlwe,
                                           void* d_scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* SHAKE128 sponges on the device (the Jindo transcript, the projection XOF)              */
+/* ------------------------------------------------------------------------------------ */
+/* n_states independent SHAKE128 sponges (golang.org/x/crypto/sha3 NewShake128) that move in
+ * lockstep: every state absorbs, and squeezes, the same number of bytes in every call, each state its
+ * own bytes.  The position in the block and the phase (absorbing or squeezing) are therefore facts
+ * of the handle on the host; only the [n_states][25] words live on the device.
+ *
+ *   rg_xof_create        n_states zeroed sponges, absorbing, at position 0
+ *   rg_xof_reset_dev     sha3's Reset(): zeroed and absorbing again
+ *   rg_xof_copy_dev      Clone(): dst takes src's words, position and phase
+ *   rg_xof_absorb_dev    state s absorbs the len bytes at d_bytes + s * state_stride; stride 0 gives
+ *                        every state the same bytes.  Any pointer alignment, stride and len (0 too).
+ *   rg_xof_absorb_plan_dev  every state absorbs the message a plan describes (below)
+ *   rg_xof_squeeze_dev   state s writes the next len bytes of its output at d_out + s * out_stride;
+ *                        the bytes between len and out_stride are not touched.  The first squeeze
+ *                        pads and permutes; later ones continue the same stream (Go's Read of 16
+ *                        bytes, cols times over, is one stream).  Absorbing after a squeeze is
+ *                        RG_ERR_INVALID (the reference panics); reset returns the handle to absorbing.
+ *
+ * A plan is the serialisation of one message as a flat list of segments, absorbed in order:
+ *   base == RG_XOF_LITERAL   len bytes at `offset` of the plan's literal blob, which is copied to the
+ *                            device once, at creation, and is the same for every state
+ *   any other base           for state s, len bytes at d_bases[base] + offset + s * state_stride
+ * Lattigo's Poly.WriteTo framing is not pinned by this library: the caller states the framing bytes
+ * as literals, and the residue rows are segments into the buffers rg_jindo_commit_dev and
+ * rg_jindo_eval_open_multi_dev leave behind (a coefficient is a little-endian uint64 there as in
+ * Lattigo's serialisation).  Up to 65,536 segments and RG_XOF_MAX_BASES bases; the base pointers
+ * travel as kernel arguments, so one plan serves every batch.  rg_xof_plan_bytes: the bytes each
+ * state absorbs (0 for NULL).
+ *
+ * Every _dev call is asynchronous on `stream`: nothing is allocated, freed, copied to the host or
+ * waited for inside, and each is one stream item whatever n_states, len and the segment count.
+ * RG_ERR_INVALID, with the reason in rg_last_error (it starts "xof:") and before the device is
+ * touched or the handle changed: a NULL argument (d_bytes / d_out may be NULL when len is 0);
+ * n_states of 0; a segment whose base is outside [-1, n_bases) or whose base pointer is NULL; a
+ * literal run past the blob; n_bases above RG_XOF_MAX_BASES; out_stride < len with more than one
+ * state; a copy between handles of different n_states; absorbing after a squeeze.
+ * A handle is NOT safe for concurrent calls: its position and phase change with every call, so one
+ * thread at a time, and calls on one handle take effect in the order they are issued on one stream. */
+typedef struct rg_xof rg_xof;
+typedef struct rg_xof_plan rg_xof_plan;
+#define RG_XOF_LITERAL (-1)
+#define RG_XOF_MAX_BASES 8
+typedef struct
+{
+  int base;
+  size_t offset, state_stride, len;
+} rg_xof_seg;
+
+rg_status rg_xof_create(size_t n_states, rg_xof** out);
+void rg_xof_destroy(rg_xof* x);
+rg_status rg_xof_reset_dev(rg_xof* x, void* stream);
+rg_status rg_xof_copy_dev(rg_xof* dst, const rg_xof* src, void* stream);
+rg_status rg_xof_absorb_dev(rg_xof* x, const uint8_t* d_bytes, size_t len, size_t state_stride, void* stream);
+rg_status rg_xof_plan_create(const rg_xof_seg* segs, size_t n_segs, const uint8_t* literals, size_t literal_len,
+                             rg_xof_plan** out);
+void rg_xof_plan_destroy(rg_xof_plan* p);
+size_t rg_xof_plan_bytes(const rg_xof_plan* p);
+rg_status rg_xof_absorb_plan_dev(rg_xof* x, const rg_xof_plan* p, const void* const* d_bases, size_t n_bases,
+                                 void* stream);
+rg_status rg_xof_squeeze_dev(rg_xof* x, uint8_t* d_out, size_t len, size_t out_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Device memory helpers (so a cgo caller needs no HIP headers)                           */

@@ -35,6 +35,8 @@ enum class Knob : int {
   JindoUniTries,  // RINGO_JINDO_UNI_TRIES n: uniform_whole_kernel gives up after n tries (tests the fix-up path)
   JindoCdtPath,   // RINGO_JINDO_CDT_PATH exact: cdt2_noise_kernel's exact path for every sample; sum: and its
                   //                      exact sum for every v0 != v1 tail (tests the paths draws never reach)
+  XofLayout,      // RINGO_XOF_LAYOUT     lane: the SHAKE128 sponges one state per lane (xof.hip), read when a
+                  //                      handle is created
   Count
 };
 const char* knob(Knob k);

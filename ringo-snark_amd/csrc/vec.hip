@@ -129,6 +129,37 @@ static rg_status vec_L(const rg_field* f, int op, uint64_t* out, const uint64_t*
   }
 }
 
+// Uint.Marshal(): x R^-1 (a Montgomery product with the integer 1) as 8 L big-endian bytes; one lane
+// per element, bytewise stores (any output alignment; n is a handful of evaluation points).
+template <int L>
+struct MarshalArgs {
+  uint8_t* out;
+  const uint64_t* x;
+  long long n;
+  size_t x_stride, out_stride;
+  FieldParams<L> F;
+};
+
+template <int L>
+__global__ __launch_bounds__(256) void marshal_kernel(MarshalArgs<L> a) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= a.n) return;
+  uint64_t x[L], one[L], z[L];
+  const uint64_t* p = a.x + (size_t)k * a.x_stride * L;
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    x[l] = p[l];
+    one[l] = l == 0 ? 1 : 0;
+  }
+  f_mul<L>(z, x, one, a.F);
+  uint8_t* o = a.out + (size_t)k * a.out_stride;
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+#pragma unroll
+    for (int b = 0; b < 8; ++b) o[8 * l + b] = (uint8_t)(z[L - 1 - l] >> (56 - 8 * b));
+  }
+}
+
 }  // namespace rg
 
 using namespace rg;
@@ -142,6 +173,30 @@ rg_status rg_vec_dev(const rg_field* f, int op, uint64_t* d_out, const uint64_t*
   if (!d_out || !d_a || (op != RG_VEC_NEG && !d_b)) return RG_ERR_INVALID;
   hipStream_t st = as_stream(stream);
   return dispatch_limbs(f->L, [&](auto Lc) { return vec_L<Lc()>(f, op, d_out, d_a, d_b, n, st); });
+}
+
+rg_status rg_field_marshal_dev(const rg_field* f, const uint64_t* d_x, size_t n, size_t x_stride, uint8_t* d_out,
+                               size_t out_stride, void* stream) {
+  const char* why = !f ? "NULL field" : (!d_x || !d_out) ? "NULL buffer" : x_stride == 0 ? "x_stride is 0"
+                    : (n > 1 && out_stride < 8 * (size_t)f->L) ? "out_stride < 8 * L" : nullptr;
+  if (why) {
+    set_last_error(std::string("field marshal: ") + why);
+    return RG_ERR_INVALID;
+  }
+  if (n == 0) return RG_OK;
+  hipStream_t st = as_stream(stream);
+  return dispatch_limbs(f->L, [&](auto Lc) {
+    constexpr int L = Lc();
+    MarshalArgs<L> a;
+    a.out = d_out;
+    a.x = d_x;
+    a.n = (long long)n;
+    a.x_stride = x_stride;
+    a.out_stride = out_stride;
+    a.F = field_params<L>(f);
+    hipLaunchKernelGGL((marshal_kernel<L>), dim3(grid256(a.n)), dim3(256), 0, st, a);
+    return check_launch("field_marshal");
+  });
 }
 
 rg_status rg_vec(const rg_field* f, int op, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t n) {

@@ -43,6 +43,12 @@ class JindoSeedsC(ctypes.Structure):
                                                      "mlwe_round", "uniform"]]
 
 
+class XofSegC(ctypes.Structure):
+    """rg_xof_seg"""
+    _fields_ = [("base", ctypes.c_int), ("offset", ctypes.c_size_t), ("state_stride", ctypes.c_size_t),
+                ("len", ctypes.c_size_t)]
+
+
 class JindoParamsC(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in
                 ["rank", "rows", "cols", "slots", "exp", "d", "in_msis", "out_msis", "mlwe", "dcmp",
@@ -246,6 +252,17 @@ _SIGS = {
                                                     ctypes.c_size_t, vp, ctypes.c_size_t] + [vp] * 7),
     "rg_jindo_eval_respond_multi_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_size_t]),
     "rg_jindo_eval_respond_multi_dev": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t] + [vp] * 5),
+    "rg_field_marshal_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+    "rg_xof_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_xof_destroy": (None, [vp]),
+    "rg_xof_reset_dev": (ctypes.c_int, [vp, vp]),
+    "rg_xof_copy_dev": (ctypes.c_int, [vp, vp, vp]),
+    "rg_xof_absorb_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]),
+    "rg_xof_plan_create": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]),
+    "rg_xof_plan_destroy": (None, [vp]),
+    "rg_xof_plan_bytes": (ctypes.c_size_t, [vp]),
+    "rg_xof_absorb_plan_dev": (ctypes.c_int, [vp, vp, ctypes.POINTER(vp), ctypes.c_size_t, vp]),
+    "rg_xof_squeeze_dev": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]),
     "rg_malloc": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_size_t]),
     "rg_free": (ctypes.c_int, [vp]),
     "rg_memcpy_h2d": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp]),

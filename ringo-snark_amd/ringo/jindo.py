@@ -394,11 +394,129 @@ class Prover:
             _addr(pf_mlwe, n * _words(es["pf_mlwe"])), _addr(scratch, self.eval_respond_multi_scratch_bytes(n) // 8),
             _stream(stream)))
 
+    def evaluate_multi_transcript_dev(self, tr, com, incom, enc, mlwe, open_proof_stride, open_commit_stride, x,
+                                      x_stride, batch_bytes, chal_bytes, ob_enc, ob_mlwe, pf_incom, pf_partial, pf_enc,
+                                      pf_mlwe, open_scratch, respond_scratch, stream=None):
+        """Prover.Evaluate (prover.go:220-316) of tr.n proofs with the transcript on the device, queued on
+        `stream` with no host step in between: tr.open_dev (marshal x, absorb the crs, the commitments `com`
+        and x, derive batch_bytes), eval_open_multi_dev, tr.respond_dev (absorb pf_partial, derive chal_bytes),
+        eval_respond_multi_dev.  tr: a Transcript of this parameter set; batch_bytes [n][batch][16] and
+        chal_bytes [n][cols][16] are uint8 device buffers the transcript writes; everything else as the
+        two eval calls take it (batch_bytes = ob_enc = ob_mlwe = None iff batch == 1)."""
+        n, batch = tr.n, tr.batch
+        tr.open_dev(com, x, x_stride, batch_bytes, stream)
+        self.eval_open_multi_dev(n, batch, incom, enc, mlwe, open_proof_stride, open_commit_stride, x, x_stride,
+                                 batch_bytes, ob_enc, ob_mlwe, pf_incom, pf_partial, open_scratch, stream)
+        tr.respond_dev(pf_partial, chal_bytes, stream)
+        if batch == 1:
+            self.eval_respond_multi_dev(n, enc, mlwe, open_proof_stride, chal_bytes, pf_enc, pf_mlwe, respond_scratch,
+                                        stream)
+        else:
+            self.eval_respond_multi_dev(n, ob_enc, ob_mlwe, 1, chal_bytes, pf_enc, pf_mlwe, respond_scratch, stream)
+
     def challenge_bound(self):
         """Parameters.ChallengeBound() (params.go:357-360)."""
         b, ps = ctypes.c_uint64(), self.params.c_struct()
         check(lib().rg_jindo_challenge_bound(ctypes.byref(ps), ctypes.byref(b)))
         return b.value
+
+
+def transcript_plans(params, crs, batch, poly_prefix, row_prefix, com_proof_stride=None, com_commit_stride=1):
+    """The two absorb plans (xof.Plan) of the Jindo transcript (prover.go:220-302, verifier.go:56-96) for one
+    parameter set, a state per proof:
+
+      A  the crs (CommitKey.WriteRawTo), then each of the `batch` commitments' out_msis polynomials
+         (Commitment.WriteRawTo), then x.Marshal().  Bases: 0 = the commitments, commitment t of proof p
+         starting p * com_proof_stride + t * com_commit_stride commitments in (default (batch, 1): a
+         [proof][commit][out_msis][nq][d] buffer; (1, n_proofs) reads the [commit][proof] buffer one
+         commit_dev per round leaves behind); 1 = [n_proofs][8 * L] marshalled points (xof.marshal_dev).
+      B  the cols + 1 polynomials of Partial / PartialMask.  Base 0 = pf_partial [n_proofs][cols+1][nq][d].
+
+    The framing is the CALLER'S statement of Lattigo's ring.Poly.WriteTo, which is not in the reference
+    tree and so is not pinned here: a polynomial of `levels` rows of n coefficients is written as
+    poly_prefix(levels, n), then per row row_prefix(n) and the n coefficients as little-endian uint64,
+    which is how the device holds a residue row.  Both callbacks return bytes (possibly empty).
+    A plan holds at most 65,536 segments (one per row and one per distinct prefix run); xof.Plan raises
+    for a set that needs more (batch 4096)."""
+    from . import xof
+    P = params
+    row = P.d * 8
+    pp, rp = bytes(poly_prefix(P.nq, P.d)), bytes(row_prefix(P.d))
+    crs = bytes(crs)
+    lit = crs + pp + rp
+    o_pp, o_rp = len(crs), len(crs) + len(pp)
+
+    def poly(segs, base, word_offset, stride):
+        """one [nq][d] polynomial at `word_offset` words of base"""
+        if pp or rp:
+            segs.append((xof.LITERAL, o_pp, 0, len(pp) + len(rp)))  # the polynomial's prefix and its first row's: one run
+        for l in range(P.nq):
+            if l and rp:
+                segs.append((xof.LITERAL, o_rp, 0, len(rp)))
+            segs.append((base, (word_offset + l * P.d) * 8, stride, row))
+
+    com_words = P.out_msis * P.nq * P.d
+    ps = batch if com_proof_stride is None else com_proof_stride
+    a = [(xof.LITERAL, 0, 0, len(crs))]
+    for t in range(batch):
+        for i in range(P.out_msis):
+            poly(a, 0, t * com_commit_stride * com_words + i * P.nq * P.d, ps * com_words * 8)
+    a.append((1, 0, 8 * P.L, 8 * P.L))
+    b = []
+    for i in range(P.cols + 1):
+        poly(b, 0, i * P.nq * P.d, (P.cols + 1) * P.nq * row)
+    return xof.Plan(a, lit), xof.Plan(b, lit)
+
+
+class Transcript:
+    """The Fiat-Shamir transcripts of n_proofs proofs of one parameter set on the device: the two plans of
+    transcript_plans, the sponges (ringo.xof.Shake128) and the marshalled points.  open_dev and respond_dev
+    only queue work on `stream`: nothing is copied to the host or waited for, so a batch Evaluate
+    (Prover.evaluate_multi_transcript_dev) or Verify (Verifier.verify_multi_transcript_dev) is one
+    uninterrupted queue.  Not safe for concurrent use, and one batch at a time: open_dev restarts it.
+
+    Use it for large batches only.  Measured (profiles/xof_transcript_timing.txt, README "Transcript on the
+    device"): the whole batched Evaluate with this transcript is faster than the host transcript between
+    the two calls at 64 proofs (48.4 against 94.7 us per proof at t14_b1, 1,114 against 1,767 us at
+    mult_t8193_b12) and slower at 1 and 8 proofs (a sponge is a serial chain, ~6 us per 168 bytes, whose
+    time does not shrink with the batch): there keep the host flow (eval_open_multi_dev, hashlib / sha3,
+    eval_respond_multi_dev)."""
+
+    def __init__(self, params, crs, batch, n_proofs, poly_prefix, row_prefix, com_proof_stride=None,
+                 com_commit_stride=1):
+        import torch
+
+        from . import xof
+        from .bigpoly import Field
+        self.params, self.batch, self.n = params, batch, n_proofs
+        self.plan_a, self.plan_b = transcript_plans(params, crs, batch, poly_prefix, row_prefix, com_proof_stride,
+                                                    com_commit_stride)
+        self.field = Field(params.field_q, limbs=params.L)
+        self.h = xof.Shake128(n_proofs)
+        self.fork = xof.Shake128(n_proofs) if batch > 1 else None
+        self.x_bytes = torch.empty(n_proofs * 8 * params.L, dtype=torch.uint8,
+                                   device=torch.device("cuda", torch.cuda.current_device()))
+
+    def open_dev(self, com, x, x_stride, batch_bytes, stream=None):
+        """prover.go:220-248: x.Marshal(), absorb plan A; with batch > 1, fork (the copy replaces the
+        reference's Reset-and-rewrite), squeeze batch * 16 bytes per proof from the fork into batch_bytes
+        [n_proofs][batch][16] and absorb them into the original.  batch_bytes is None iff batch == 1."""
+        from . import xof
+        if (batch_bytes is None) != (self.batch == 1):
+            raise RingoPanic("batch_bytes is None iff batch == 1")
+        xof.marshal_dev(self.field, x, self.n, x_stride, self.x_bytes, stream=stream)
+        self.h.reset(stream)
+        self.h.absorb_plan(self.plan_a, [com, self.x_bytes], stream)
+        if self.batch > 1:
+            self.fork.copy_from(self.h, stream)
+            self.fork.squeeze(batch_bytes, self.batch * 16, stream=stream)
+            self.h.absorb(batch_bytes, self.batch * 16, stream=stream)
+
+    def respond_dev(self, pf_partial, chal_bytes, stream=None):
+        """prover.go:291-302: absorb Partial / PartialMask (plan B over pf_partial), squeeze cols * 16 bytes
+        per proof into chal_bytes [n_proofs][cols][16]."""
+        self.h.absorb_plan(self.plan_b, [pf_partial], stream)
+        self.h.squeeze(chal_bytes, self.params.cols * 16, stream=stream)
 
 
 def _byte_addr(x, nbytes):
@@ -535,6 +653,22 @@ class Verifier:
             _addr(pf_partial, n * (P.cols + 1) * pq), _addr(pf_enc, n * P.rows * pq), _addr(pf_mlwe, n * nm * pq),
             float(P.in_com_dcmp_two_nm), float(P.res_two_nm), _addr(out, n * VERIFY_WORDS),
             _addr(scratch, self.verify_multi_scratch_bytes(n, batch) // 8), _stream(stream)))
+
+    def verify_multi_transcript_dev(self, tr, com, x, x_stride, y, pf_incom, pf_partial, pf_enc, pf_mlwe, batch_bytes,
+                                    chal_bytes, bq, bo, chals, left, right, out, inputs_scratch, verify_scratch,
+                                    stream=None):
+        """Verifier.Verify (verifier.go:56-133) of tr.n proofs with the transcript replayed on the device,
+        queued on `stream` with no host step in between: tr.open_dev and tr.respond_dev over the proofs'
+        Partial (the bytes land in batch_bytes / chal_bytes), verify_inputs_multi_dev, verify_multi_dev.
+        bq, bo, chals, left, right are the buffers verify_inputs_multi_dev fills; batch_bytes = bq = bo =
+        None iff batch == 1; out [n][VERIFY_WORDS] as verify_multi_dev."""
+        n, batch = tr.n, tr.batch
+        tr.open_dev(com, x, x_stride, batch_bytes, stream)
+        tr.respond_dev(pf_partial, chal_bytes, stream)
+        self.verify_inputs_multi_dev(n, batch, x, x_stride, batch_bytes, chal_bytes, bq, bo, chals, left, right,
+                                     inputs_scratch, stream)
+        self.verify_multi_dev(n, batch, com, bq, bo, chals, left, right, y, pf_incom, pf_partial, pf_enc, pf_mlwe, out,
+                              verify_scratch, stream)
 
     def unpack_verify_words(self, words):
         """The records of verify_multi_dev (host words [n][VERIFY_WORDS]) as verify_dev's result objects."""
